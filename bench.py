@@ -24,8 +24,18 @@ the max-over-ranks reduction. Under torchrun (WORLD_SIZE set) this process is on
 child processes, before anything touches the GPU), waits for them and exits with the
 first failing rank's status. Rank 0 prints the JSON line.
 
-The JSON line also carries:
-  roofline      the transport kernel (k_step: one launch that seals and then opens the batch)
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline figure needs and no more:
+it sets up, ramps, runs the W warmup steps, times the N steps and prints the JSON line (metric, value,
+unit, ms_per_step, how the steps were launched, the configuration). --dump-outputs DIR also writes, right
+after the timed steps, what the last step left in the caller's buffers for a fixed seeded sample of
+packets (as many as fit 48 MiB): DIR/packets.npy (their numbers), ct.npy (each one's ct || tag bytes),
+pt.npy (its opened plaintext), status.npy (its open status), all float32. The inputs are seeded, so two
+builds run with the same arguments can be compared file for file.
+
+With --full the run goes on after the timed steps and the JSON line also carries:
+  verified      open(seal(x)) == x on the device for every packet the timed launches wrote, every status OK
+                (and the oracle sample below); a failure on any rank makes the run exit 3
+  roofline     the transport kernel (k_step: one launch that seals and then opens the batch)
                 against the 8 TB/s HBM peak: achieved = sum(4L + 32) per step / GPU time per step
                 (SURVEY.md §8d), GPU time from HIP events on the launch stream around
                 the timed region; `traffic` = HBM bytes per launch from the committed
@@ -268,6 +278,36 @@ def pmc_traffic(workload="c1", mode="serial"):
     return round(v) if v is not None else None
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs writes at most this much (float32), all files together
+
+
+def dump_sample(strides: np.ndarray) -> np.ndarray:
+    """--dump-outputs: the packets whose outputs are written, a fixed seeded draw (the same for every run
+    of the same workload), as many as fit the byte budget: each packet costs its ct || tag and its plaintext
+    (at most 2 x stride bytes) and one status, 4 bytes per value as float32."""
+    n = len(strides)
+    order = np.random.default_rng(20260).permutation(n)
+    cost = np.cumsum(4 * (2 * strides[order].astype(np.int64) + 1))
+    return np.sort(order[:int(np.searchsorted(cost, DUMP_BUDGET_BYTES, side="right"))])
+
+
+def dump_index(off, lens, pick) -> np.ndarray:
+    """Byte indices of lens[i] bytes from off[i] for every picked packet, in packet order."""
+    ln = np.asarray(lens, np.int64)[pick]
+    start = np.asarray(off, np.int64)[pick]
+    first = np.cumsum(ln) - ln
+    return np.repeat(start - first, ln) + np.arange(int(ln.sum()), dtype=np.int64)
+
+
+def dump_write(out_dir: str, rank: int, world: int, arrays: dict) -> None:
+    """DIR/<name>.npy in float32 (bytes, statuses and packet numbers are exact in it); the ranks of a
+    multi-GPU run write <name>_rank<r>.npy each."""
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{tag}.npy"), np.asarray(a).astype(np.float32))
+
+
 def host_bench(args):
     """configs[4]: tun ring -> seal -> UDP ring -> open -> tun ring, buffers in host memory."""
     import torch
@@ -305,6 +345,11 @@ def host_bench(args):
         t2 = time.perf_counter()
         seal_t += t1 - t0
         open_t += t2 - t1
+    if args.dump_outputs:  # the last step's UDP ring (ct || tag), plaintext ring and statuses, sampled
+        pick = dump_sample(np.full(n, wire, np.int64))
+        dump_write(args.dump_outputs, 0, 1, {
+            "packets": pick, "ct": np.asarray(ring)[dump_index(sd["out_off"], np.full(n, L + 16), pick)],
+            "pt": np.asarray(back)[dump_index(od["out_off"], np.full(n, L), pick)], "status": np.asarray(st)[pick]})
     ok = not st.any() and np.array_equal(back.reshape(n, tun_stride)[:, :L], tun.reshape(n, tun_stride)[:, :L])
     payload = 2.0 * n * L * args.steps
     mode = os.environ.get("WG_HOST_PATH", "auto")
@@ -427,7 +472,17 @@ def main():
     # diagnostic knobs (not the metric's configuration): batch size and session count of C1 / C2
     ap.add_argument("--packets", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--keys", type=int, default=0, help=argparse.SUPPRESS)
+    # a plain run sets up, warms up, times the steps and prints the headline line; --full adds everything
+    # else the line can carry (the checks, the roofline's extra timings, the CPU baseline; module docstring)
+    ap.add_argument("--full", action="store_true",
+                    help="also check the timed outputs (round trip, oracle sample), re-time the kernel on one "
+                         "stream, time seal / open / copy trains and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed for a seeded sample of "
+                         "packets as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != args.gpus:
@@ -663,11 +718,75 @@ def main():
         dist.barrier()
     elapsed = t1 - t0
     gpu_step_ms = ev0.elapsed_time(ev1) / args.steps  # = t_seal + t_open (back-to-back launches), or t_duplex
+    window_launches = launch_count[0] - launches_before
 
+    # --dump-outputs: what the last timed step left in the caller's buffers (nothing has run since), for a
+    # seeded sample of packets: each one's ct || tag, its opened plaintext and its open status
+    if args.dump_outputs:
+        pick = dump_sample(S)
+        ct_last = cts[(k_step[0] - 1) & 1] if args.mode == "duplex" else ct
+        # stream B's packets report through its ring of statuses, whose first m entries are its half in order
+        st_all = status if st2 is None else torch.cat([status[:cuts[1]], st2[:n - cuts[1]]])
+        d_pick = torch.from_numpy(pick).to(dev)
+        dump_write(args.dump_outputs, rank, world, {
+            "packets": pick,
+            "ct": ct_last[torch.from_numpy(dump_index(off, lengths + 16, pick)).to(dev)].cpu().numpy(),
+            "pt": back[torch.from_numpy(dump_index(off, lengths, pick)).to(dev)].cpu().numpy(),
+            "status": st_all[d_pick].cpu().numpy()})
+        del d_pick, st_all
+
+    payload = 2.0 * float(lengths.sum())  # sealed + opened bytes per step on this rank
+    D = importlib.import_module("wireguard-java_amd.dist")
+
+    def headline(elapsed, payload_all):
+        """The result line of a plain run (rank 0): the headline figure and how the steps were run."""
+        return {
+            "metric": METRIC,
+            "value": round(payload_all * args.steps / elapsed / GIB, 2),
+            "unit": "GiB/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ramp_ms": args.ramp_ms,
+            "ramp_steps": ramp_steps,
+            "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
+            "host_enqueue_ms_per_step": round((t_enq - t0) * 1e3 / args.steps, 4),
+            "graph": bool(args.graph),
+            "graph_warm_steps": args.steps if args.graph else 0,  # the graph's warm replay, before the timed one
+            # transport-kernel launches enqueued before the timed region and inside it (tools/prof_window.py)
+            "launches_before_window": launches_before if graph is None else None,
+            "window_launches": window_launches if graph is None else None,
+            "stagger": bool(stagger),
+            "spin_sync": bool(args.spin_sync),
+            "full": bool(args.full),
+            "higher_is_better": True,
+            "scaling": "strong" if args.workload == "c3" else "weak",
+            "vs_baseline": None,
+            "dtype": "u32",
+            "data": "synthetic (random payload in HBM, splitmix64 keys, sequential counters)",
+            "config": {"workload": wdesc, "packets_per_gpu": n, "payload_bytes": int(lengths.mean()), "step": args.mode,
+                       "streams": K,
+                       "sessions_per_gpu": nkeys, "parallelism": f"dp{world} sharded by session, no collective",
+                       **({"rehearsal": f"{world} ranks on cuda:0, report over {args.dist_backend}"}
+                          if args.same_device else {})},
+            "gpu_ms_per_step": round(gpu_step_ms, 5),  # HIP events around the timed region, this rank
+        }
+
+    if not args.full:  # a plain run ends here: the max-over-ranks time, the payload sum, the line
+        payload_all = payload
+        if use_dist:
+            (elapsed,), payload_all, _ = D.reduce_report(dist, rdev, [elapsed], payload, True)
+        if rank == 0:
+            print(json.dumps(headline(elapsed, payload_all)), flush=True)
+        eng.close()
+        if use_dist:
+            dist.destroy_process_group()
+        return
+
+    # --full from here on.
     # correctness guard on the device, on the buffers the timed launches wrote (nothing has run since):
     # open(seal(x)) == x with every tag verified, and below the ct||tag of a seeded sample against the
     # oracle. The re-timing and the per-kernel trains after this overwrite ct / back / status.
-    window_launches = launch_count[0] - launches_before
     if st2 is not None:  # stream B's packets report through its ring of statuses
         ok_status = int(status[:cuts[1]].abs().sum().item()) == 0 and int(st2[:st2_used].abs().sum().item()) == 0
     else:
@@ -752,8 +871,6 @@ def main():
     sample_res = oracle_sample_check(sample, keys) if sample is not None else None
     sample_ok = sample_res is None or sample_res["bit_exact"]
 
-    payload = 2.0 * float(lengths.sum())  # sealed + opened bytes per step on this rank
-    D = importlib.import_module("wireguard-java_amd.dist")
     # transport kernel launches per step: k_duplex, or k_step (one WG_F_AFTER_SEAL step), or seal + open
     fused_step = args.mode == "step" and args.kernel in ("default", "transport") and args.variant == 0
     launches = (1 if (args.mode == "duplex" or fused_step) else 2) * (K if args.mode != "duplex" else 1)
@@ -769,7 +886,6 @@ def main():
         payload_all = payload
         all_ok = ok_status and ok_data and sample_ok
 
-    value = payload_all * args.steps / elapsed / GIB
     # seal reads L, writes L+16; open reads L+16, writes L -> 4L+32 per packet
     step_alg = float((4 * lengths + 32).sum())
     step_rate = step_alg / (gpu_step_ms * 1e-3) / 1e9  # the whole step (all K streams), GPU time
@@ -795,34 +911,8 @@ def main():
         base = {"default": "k_transport", "transport": "k_transport", "wave1": "k_wave", "tile": "k_tile"}[args.kernel]
         knames = [base + "<seal>", base + "<open>"]
     if rank == 0:
-        line = {
-            "metric": METRIC,
-            "value": round(value, 2),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ramp_ms": args.ramp_ms,
-            "ramp_steps": ramp_steps,
-            "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
-            "host_enqueue_ms_per_step": round((t_enq - t0) * 1e3 / args.steps, 4),
-            "graph": bool(args.graph),
-            "graph_warm_steps": args.steps if args.graph else 0,  # the graph's warm replay, before the timed one
-            # transport-kernel launches enqueued before the timed region and inside it (tools/prof_window.py)
-            "launches_before_window": launches_before if graph is None else None,
-            "window_launches": window_launches if graph is None else None,
-            "stagger": bool(stagger),
-            "spin_sync": bool(args.spin_sync),
-            "higher_is_better": True,
-            "scaling": "strong" if args.workload == "c3" else "weak",
-            "vs_baseline": None,
-            "dtype": "u32",
-            "data": "synthetic (random payload in HBM, splitmix64 keys, sequential counters)",
-            "config": {"workload": wdesc, "packets_per_gpu": n, "payload_bytes": int(lengths.mean()), "step": args.mode,
-                       "streams": K,
-                       "sessions_per_gpu": nkeys, "parallelism": f"dp{world} sharded by session, no collective",
-                       **({"rehearsal": f"{world} ranks on cuda:0, report over {args.dist_backend}"}
-                          if args.same_device else {})},
+        line = headline(elapsed, payload_all)
+        line.update({
             "roofline": {"bound": "hbm", "kernel": kname + (", one stream" if single_ms is not None else ""),
                          "achieved": round(achieved, 1),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
@@ -842,7 +932,7 @@ def main():
             "per_gpu": [{"rank": r["rank"], "gib_s": round(r["gib_s"], 2), "packets_per_step": r["packets"],
                          "elapsed_s": round(r["elapsed_s"], 6), "seal_ms": round(r["seal_ms"], 5),
                          "open_ms": round(r["open_ms"], 5), "kernel_ms": round(r["kernel_ms"], 5)} for r in per_gpu],
-        }
+        })
         if valu:
             rate = valu / (k_ms * 1e-3)
             line["valu_roofline"] = {"insts_per_launch": round(valu), "achieved": round(rate / 1e12, 4),

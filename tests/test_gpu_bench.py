@@ -67,10 +67,12 @@ def test_bench_two_stream_step_every_packet_vs_oracle(engine):
     assert np.array_equal(back[:, :L], pt.reshape(n, stride)[:, :L])
 
 
-def _bench(extra_env, steps="2", *extra):
+def _bench(extra_env, steps="2", *extra, full=True):
+    """One short bench run; with --full (the line's checks and roofline) unless full=False."""
     env = dict(os.environ, **extra_env)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--warmup", "1",
-                        "--ramp-ms", "0", *extra], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
+                        "--ramp-ms", "0", *(["--full"] if full else []), *extra],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert lines, f"no JSON line (rc {p.returncode}): {p.stderr[-2000:]}"
     return p.returncode, json.loads(lines[-1])
@@ -100,6 +102,48 @@ def test_bench_line_fails_when_k_step_writes_a_wrong_tag():
         assert line["stagger"] is True and line["window_launches"] == 2 * int(steps) + 1
     rc, line = _bench({"WG_TEST_STEP_FLIP": "64"})  # the product library: no hook, still bit-exact
     assert rc == 0 and line["verified"] is True and line["oracle_sample"]["bit_exact"] is True
+
+
+def test_plain_run_is_lean_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line only: value, ms_per_step and the launch bookkeeping,
+    none of the checks or extra timings. --dump-outputs writes the last timed step's outputs for a seeded
+    sample of packets; they are checked here against the oracle (C1: key splitmix(0xC0FFEE), counter = packet
+    number): the dumped ct || tag opens to the dumped plaintext with every tag valid, and sealing that
+    plaintext gives the dumped ct || tag bit for bit. A second run writes identical files."""
+    import bench
+    out = [str(tmp_path / "a"), str(tmp_path / "b")]
+    for d in out:
+        rc, line = _bench({}, "2", "--dump-outputs", d, full=False)
+        assert rc == 0, line
+        assert line["full"] is False and line["steps"] == 2 and line["window_launches"] == 4
+        assert line["unit"] == "GiB/s" and line["higher_is_better"] is True and line["dtype"] == "u32"
+        assert abs(line["value"] - 2 * 65536 * 1420 / (line["ms_per_step"] * 1e-3) / 2**30) < 0.01 * line["value"]
+        for k in ("roofline", "verified", "oracle_sample", "cpu_baseline", "per_gpu", "valu_roofline"):
+            assert k not in line, k
+    a = {k: np.load(os.path.join(out[0], k + ".npy")) for k in ("packets", "ct", "pt", "status")}
+    assert sorted(os.listdir(out[0])) == sorted(os.listdir(out[1])) == ["ct.npy", "packets.npy", "pt.npy", "status.npy"]
+    for k, v in a.items():
+        assert v.dtype == np.float32 and np.array_equal(v, np.load(os.path.join(out[1], k + ".npy"))), k
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BUDGET_BYTES
+    L = 1420
+    pick = a["packets"].astype(np.int64)
+    p = len(pick)
+    assert p >= 2048 and np.all(np.diff(pick) > 0) and pick[-1] < 65536
+    assert a["ct"].size == p * (L + 16) and a["pt"].size == p * L and not a["status"].any()
+    stride = 1440
+    off = np.arange(p, dtype=np.uint64) * stride
+    desc = wg().pack_desc(off, off, pick.astype(np.uint64), L, 0)
+    keys = splitmix_np(0xC0FFEE, 32)
+    ct = np.zeros((p, stride), np.uint8)
+    ct[:, :L + 16] = a["ct"].astype(np.uint8).reshape(p, L + 16)
+    pt = np.zeros((p, stride), np.uint8)
+    pt[:, :L] = a["pt"].astype(np.uint8).reshape(p, L)
+    back = np.zeros(p * stride, np.uint8)
+    assert not O.open_batch(desc, ct.reshape(-1), back, keys, threads=16).any()
+    assert np.array_equal(back.reshape(p, stride)[:, :L], pt[:, :L])
+    ref = np.zeros(p * stride, np.uint8)
+    O.seal_batch(desc, pt.reshape(-1), ref, keys, threads=16)
+    assert np.array_equal(ref.reshape(p, stride)[:, :L + 16], ct[:, :L + 16])
 
 
 def test_bench_imix_fused_planning_is_verified():

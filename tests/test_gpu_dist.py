@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 def test_two_ranks_sharded_c3_on_one_gpu():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c3",
-                        "--steps", "2", "--warmup", "1", "--ramp-ms", "0", "--dist-backend", "gloo",
+                        "--steps", "2", "--warmup", "1", "--ramp-ms", "0", "--full", "--dist-backend", "gloo",
                         "--same-device"], cwd=ROOT, capture_output=True, text=True, timeout=300,
                        env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

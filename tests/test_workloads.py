@@ -30,6 +30,29 @@ def test_imix_mix():
         assert np.array_equal(ctr[slots == s], np.arange(256, dtype=np.uint64))
 
 
+def test_dump_sample_is_seeded_and_fits_the_budget(tmp_path):
+    """--dump-outputs: the sampled packets are the same for every run of a workload, fit the byte budget
+    (well under 64 MB as float32, for the largest packets too), cover a small batch whole, and dump_index
+    addresses exactly each picked packet's bytes in packet order."""
+    for name in ("c1", "c2", "imix"):
+        L = bench.build_workload(name, 0, 1)[0]
+        S = ((L + 16 + 15) // 16) * 16
+        off = np.concatenate([[0], np.cumsum(S)[:-1]])
+        pick = bench.dump_sample(S)
+        assert np.array_equal(pick, bench.dump_sample(S)) and np.all(np.diff(pick) > 0)
+        assert 1024 <= len(pick) <= len(L)
+        values = len(bench.dump_index(off, L + 16, pick)) + len(bench.dump_index(off, L, pick)) + 2 * len(pick)
+        assert 4 * values <= bench.DUMP_BUDGET_BYTES <= 64 * 10**6
+    assert np.array_equal(bench.dump_sample(np.full(5, 9024)), np.arange(5))
+    idx = bench.dump_index([0, 100, 200, 300], [3, 0, 2, 4], np.array([0, 1, 3]))
+    assert idx.tolist() == [0, 1, 2, 300, 301, 302, 303]
+    bench.dump_write(str(tmp_path / "d"), 0, 1, {"status": np.array([0, 1, -1], np.int32), "ct": np.arange(256, dtype=np.uint8)})
+    assert np.load(tmp_path / "d" / "ct.npy").dtype == np.float32
+    assert np.load(tmp_path / "d" / "status.npy").tolist() == [0.0, 1.0, -1.0]
+    bench.dump_write(str(tmp_path / "d"), 1, 2, {"ct": np.zeros(1, np.uint8)})
+    assert (tmp_path / "d" / "ct_rank1.npy").exists()
+
+
 def _cgroup(tmp_path, quota_cpus):
     """A cgroup v2 root whose cpu.max allows `quota_cpus` CPUs of time (None: no quota)."""
     root = tmp_path / f"cg{quota_cpus}"

@@ -13,7 +13,7 @@ tail -3 $O/gpu_tests.log
 for k in default wave1; do
   for w in c1 c2; do
     echo "[ab] bench $w $k"
-    timeout -k 10 300 python bench.py --workload $w --kernel $k --no-cpu-baseline > $O/bench_${w}_$k.json 2>> $O/bench.err
+    timeout -k 10 300 python bench.py --full --workload $w --kernel $k --no-cpu-baseline > $O/bench_${w}_$k.json 2>> $O/bench.err
     cat $O/bench_${w}_$k.json
   done
 done

@@ -24,7 +24,7 @@ for r in $(seq 1 ${AB_REPS:-2}); do
     for w in ${AB_WORKLOADS:-c1 c2}; do
       envs=""; args=""
       for x in $a; do case $x in --*) args="$args $x";; *=*) envs="$envs $x";; *) args="$args $x";; esac; done
-      env $envs timeout -k 10 200 python bench.py --workload $w --no-cpu-baseline $AB_BENCH_ARGS $args > $O/v${i}_${w}_$r.json 2>> $O/err.log || { echo "[$a] $w bench failed"; tail -5 $O/err.log; exit 1; }
+      env $envs timeout -k 10 200 python bench.py --full --workload $w --no-cpu-baseline $AB_BENCH_ARGS $args > $O/v${i}_${w}_$r.json 2>> $O/err.log || { echo "[$a] $w bench failed"; tail -5 $O/err.log; exit 1; }
       python3 -c "import json; d=json.load(open('$O/v${i}_${w}_$r.json')); print('[$a] $w $r', d['value'], d['roofline']['kernel_ms'], d['roofline']['frac'], d['verified'])"
     done
   done

@@ -31,7 +31,7 @@ run() {  # name env... -- bench args
   local envs=()
   while [ "$1" != "--" ]; do envs+=("$1"); shift; done
   shift
-  env "${envs[@]}" timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > $O/tmp.json 2>> $O/bench.err || die "bench $name $*" $?
+  env "${envs[@]}" timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > $O/tmp.json 2>> $O/bench.err || die "bench $name $*" $?
   python3 - "$name" "$*" $O/tmp.json >> $O/ab.jsonl <<'EOF'
 import json, sys
 d = json.load(open(sys.argv[3]))

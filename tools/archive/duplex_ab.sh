@@ -13,12 +13,12 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_duplex.py tests/test_gpu_pa
 tail -2 $O/tests.log
 for run in "serial:--mode serial" "duplex:--mode duplex" "streams2:--streams 2" "duplex_c2:--mode duplex --workload c2" "serial_c2:--mode serial --workload c2"; do
   name=${run%%:*}; a=${run#*:}
-  timeout -k 10 300 python bench.py $a --no-cpu-baseline > $O/bench_$name.json 2>> $O/bench.err
+  timeout -k 10 300 python bench.py --full $a --no-cpu-baseline > $O/bench_$name.json 2>> $O/bench.err
   python3 -c "import json; d=json.load(open('$O/bench_$name.json')); print('$name', d['value'], d['roofline']['kernel_ms'], d['roofline']['frac'], d['verified'])"
 done
-WG_LIB_PATH=$ROOT/wireguard-java_amd/libwgaead_split.so timeout -k 10 300 python bench.py --mode duplex --no-cpu-baseline > $O/bench_duplex_split.json 2>> $O/bench.err
+WG_LIB_PATH=$ROOT/wireguard-java_amd/libwgaead_split.so timeout -k 10 300 python bench.py --full --mode duplex --no-cpu-baseline > $O/bench_duplex_split.json 2>> $O/bench.err
 python3 -c "import json; d=json.load(open('$O/bench_duplex_split.json')); print('duplex_split', d['value'], d['roofline']['kernel_ms'], d['roofline']['frac'], d['verified'])"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 $ROOT/bench.py --mode duplex --no-cpu-baseline > $O/prof_bench.json 2> $O/prof.log
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 $ROOT/bench.py --full --mode duplex --no-cpu-baseline > $O/prof_bench.json 2> $O/prof.log
 cat $O/prof_bench.json
 echo "[dx] done"

@@ -12,6 +12,6 @@ for lib in "$@"; do
   echo "$lib $(tail -1 $O/${lib}_tests.log)"
 done
 for r in 1 2; do for lib in "$@"; do for w in ${AB_WORKLOADS:-c1 c2}; do
-  WG_LIB_PATH=$ROOT/wireguard-java_amd/$lib timeout -k 10 200 python bench.py --workload $w --no-cpu-baseline $AB_ARGS > $O/${lib}_${w}_$r.json 2>> $O/err.log || { echo "$lib $w bench failed"; exit 1; }
+  WG_LIB_PATH=$ROOT/wireguard-java_amd/$lib timeout -k 10 200 python bench.py --full --workload $w --no-cpu-baseline $AB_ARGS > $O/${lib}_${w}_$r.json 2>> $O/err.log || { echo "$lib $w bench failed"; exit 1; }
   python3 -c "import json; d=json.load(open('$O/${lib}_${w}_$r.json')); print('$lib $w $r', d['value'], d['roofline']['kernel_ms'], d['roofline']['frac'], d['verified'])"
 done; done; done

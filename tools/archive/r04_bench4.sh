@@ -7,7 +7,7 @@ mkdir -p $out
 for w in c1 c2 c3 c1b; do
   wl=${w%b}; extra=""
   [ $wl = c3 ] && extra="--steps 5 --warmup 1"
-  timeout -k 10 300 python bench.py --workload $wl $extra > $out/$w.json 2>>$out/err || exit 1
+  timeout -k 10 300 python bench.py --full --workload $wl $extra > $out/$w.json 2>>$out/err || exit 1
   python3 - $out/$w.json <<'PY' || exit 1
 import json,sys
 j=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

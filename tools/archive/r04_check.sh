@@ -18,12 +18,12 @@ timeout -k 10 120 ./tools/batcher_bench 1 300 1420 gap_us=2000 >> $O/batcher.jso
 timeout -k 10 120 ./tools/batcher_bench 16 2000 1420 hold_us=50000 >> $O/batcher.jsonl || exit 1
 cut -c1-300 $O/batcher.jsonl
 step bench_c1
-timeout -k 10 300 python bench.py > $O/c1.json 2> $O/bench.err || exit 1
+timeout -k 10 300 python bench.py --full > $O/c1.json 2> $O/bench.err || exit 1
 cat $O/c1.json
 step bench_c1_graph
-timeout -k 10 300 python bench.py --graph --no-cpu-baseline > $O/c1_graph.json 2>> $O/bench.err || exit 1
+timeout -k 10 300 python bench.py --full --graph --no-cpu-baseline > $O/c1_graph.json 2>> $O/bench.err || exit 1
 step bench_c2
-timeout -k 10 300 python bench.py --workload c2 > $O/c2.json 2>> $O/bench.err || exit 1
+timeout -k 10 300 python bench.py --full --workload c2 > $O/c2.json 2>> $O/bench.err || exit 1
 step bench_c3
-timeout -k 10 300 python bench.py --workload c3 --steps 5 --warmup 1 > $O/c3.json 2>> $O/bench.err || exit 1
+timeout -k 10 300 python bench.py --full --workload c3 --steps 5 --warmup 1 > $O/c3.json 2>> $O/bench.err || exit 1
 step done

@@ -9,7 +9,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smok
 tail -1 $out/smoke.log
 for w in c1 c2 c3 c1b; do
   wl=${w%b}; extra=""; [ $wl = c3 ] && extra="--steps 5 --warmup 1"
-  timeout -k 10 300 python bench.py --workload $wl $extra > $out/$w.json 2>>$out/err || exit 1
+  timeout -k 10 300 python bench.py --full --workload $wl $extra > $out/$w.json 2>>$out/err || exit 1
   python3 -c "
 import json; j=json.loads(open('$out/$w.json').read().strip().splitlines()[-1]); r=j['roofline']
 print('$w', j['value'], j['ms_per_step'], r['frac'], r['step']['frac'], r.get('traffic'), j['verified'], j['oracle_sample']['bit_exact'], j['cpu_baseline']['value'])"

@@ -10,7 +10,7 @@ for k in 1 2 3; do
   for v in h2 h1; do
     lib=""; [ $v = h1 ] && lib="build_ab/libwgaead_h1.so"
     for w in c1 c2; do
-      WG_LIB_PATH=$lib timeout -k 10 200 python bench.py --workload $w --no-cpu-baseline > $out/${w}_${v}_$k.json 2>>$out/err || exit 1
+      WG_LIB_PATH=$lib timeout -k 10 200 python bench.py --full --workload $w --no-cpu-baseline > $out/${w}_${v}_$k.json 2>>$out/err || exit 1
       python3 -c "
 import json; j=json.loads(open('$out/${w}_${v}_$k.json').read().strip().splitlines()[-1]); r=j['roofline']
 print('$w $v', j['value'], j['ms_per_step'], r['frac'], r['step']['frac'], j['verified'], j['oracle_sample']['bit_exact'])"

@@ -6,7 +6,7 @@ mkdir -p $O
 for rep in 1 2 3; do
   for w in c1 c2; do
     for k in 1 2; do
-      timeout -k 10 200 python bench.py --workload $w --streams $k --no-cpu-baseline > $O/b.json 2>/dev/null || exit 1
+      timeout -k 10 200 python bench.py --full --workload $w --streams $k --no-cpu-baseline > $O/b.json 2>/dev/null || exit 1
       python3 -c "
 import json; d=json.loads(open('$O/b.json').read().strip().splitlines()[-1])
 print(json.dumps({'rep': $rep, 'workload': '$w', 'streams': $k, 'value': d['value'], 'ms_per_step': d['ms_per_step']}))" | tee -a $O/streams.jsonl

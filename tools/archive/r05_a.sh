@@ -8,7 +8,7 @@ timeout -k 10 900 python -u -m pytest tests -x -v -m gpu --timeout 240 --timeout
 tail -1 $O/tests.log
 for r in 1 2; do
   for v in 1 0; do
-    WG_STEP_WPE4=$v timeout -k 10 300 python bench.py --no-cpu-baseline >> $O/wpe4_$v.jsonl 2>> $O/bench.err || { echo "bench rc $?"; exit 1; }
+    WG_STEP_WPE4=$v timeout -k 10 300 python bench.py --full --no-cpu-baseline >> $O/wpe4_$v.jsonl 2>> $O/bench.err || { echo "bench rc $?"; exit 1; }
     tail -1 $O/wpe4_$v.jsonl | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('wpe4=$v', j['value'], j['roofline']['frac'], j['roofline']['step']['frac'], j['verified'])"
   done
 done
@@ -29,7 +29,7 @@ done
 # C2: dynamic claims (k_step_claim) against the static snake, with and without the issue-priority schedule
 for r in 1 2; do
   for cfg in "WG_CLAIM=0" "WG_CLAIM=1" "WG_CLAIM=1 WG_PRIO=0"; do
-    env $cfg timeout -k 10 300 python bench.py --workload c2 --no-cpu-baseline >> $O/c2_claim.jsonl 2>> $O/bench.err || { echo "bench c2 rc $?"; exit 1; }
+    env $cfg timeout -k 10 300 python bench.py --full --workload c2 --no-cpu-baseline >> $O/c2_claim.jsonl 2>> $O/bench.err || { echo "bench c2 rc $?"; exit 1; }
     tail -1 $O/c2_claim.jsonl | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('$cfg', j['value'], j['roofline']['frac'], j['roofline']['kernel_ms'], j['verified'])"
   done
 done

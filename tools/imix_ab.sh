@@ -11,7 +11,7 @@ for rep in 1 2; do
       default) env="" ;; split1) env="WG_MIXED_SPLIT=1" ;; split2) env="WG_MIXED_SPLIT=2" ;;
       split4) env="WG_MIXED_SPLIT=4" ;; claim) env="WG_CLAIM=1" ;;
     esac
-    line=$(env $env timeout -k 10 200 python bench.py --workload imix --no-cpu-baseline --steps 100 2>> $O/imix_ab.err) || { echo "FAILED $v rc $?"; exit 1; }
+    line=$(env $env timeout -k 10 200 python bench.py --full --workload imix --no-cpu-baseline --steps 100 2>> $O/imix_ab.err) || { echo "FAILED $v rc $?"; exit 1; }
     echo "$line" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(json.dumps({'variant':'$v','rep':$rep,'gib_s':d['value'],'kernel_ms':d['roofline']['kernel_ms'],'verified':d['verified'],'bit_exact':d.get('oracle_sample',{}).get('bit_exact')}))" | tee -a $O/imix_ab.jsonl
   done
 done

@@ -10,7 +10,7 @@ done
 for r in $(seq $R); do
   for lib in "$@"; do
     for w in c1 c2; do
-      WG_LIB_PATH=$PWD/$lib timeout -k 10 300 python bench.py --workload $w --no-cpu-baseline --steps 100 --warmup 10 | sed "s|^{|{\"lib\": \"$lib\", |" >> $O/ab.jsonl || { echo "bench rc $?"; exit 1; }
+      WG_LIB_PATH=$PWD/$lib timeout -k 10 300 python bench.py --full --workload $w --no-cpu-baseline --steps 100 --warmup 10 | sed "s|^{|{\"lib\": \"$lib\", |" >> $O/ab.jsonl || { echo "bench rc $?"; exit 1; }
     done
   done
 done

@@ -17,7 +17,7 @@ for k in $KS; do
     i=$((i+1))
     echo "[pmc] $k $grp"
     timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $grp -d $O/$k/p$i -o run --output-format csv -- \
-      python3 $ROOT/bench.py --workload $W --kernel $k --steps 20 --warmup 5 --ramp-ms 100 --no-cpu-baseline > $O/$k/p$i.log 2>&1
+      python3 $ROOT/bench.py --full --workload $W --kernel $k --steps 20 --warmup 5 --ramp-ms 100 --no-cpu-baseline > $O/$k/p$i.log 2>&1
   done
 done
 echo "[pmc] done"

@@ -6,7 +6,8 @@ averages do not describe the launches the bench line's `ms_per_step` and `roofli
 from (Weak #1). bench.py's JSON line carries ramp_steps / warmup / steps and the
 kernel launches per step; this tool takes the transport kernel's dispatches in issue order,
 skips (ramp_steps + warmup) x launches, keeps the next steps x launches and reports their
-durations, the window's span and the roofline fraction recomputed from them.
+durations, the window's span and the roofline fraction recomputed from them. The line must come from
+`bench.py --full`: a plain run's line has no `roofline`.
 
 PMC passes (--pmc): the same window over a counter_collection.csv gives per-dispatch counter
 means for the timed launches.

@@ -9,7 +9,7 @@ timeout -k 10 600 python -u -m pytest -x -q --timeout 150 --timeout-method threa
 tail -1 $O/tests.log
 for a in 1 2 3; do
   for v in 0 1; do
-    WG_CLAIM=$v timeout -k 10 300 python bench.py --no-cpu-baseline --workload c2 > $O/tmp.json 2>> $O/bench.err || die "bench $v" $?
+    WG_CLAIM=$v timeout -k 10 300 python bench.py --full --no-cpu-baseline --workload c2 > $O/tmp.json 2>> $O/bench.err || die "bench $v" $?
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(json.dumps({'claim': int(sys.argv[2]), 'value': d['value'], 'ms_per_step': d['ms_per_step'], 'kernel_ms': d['roofline']['kernel_ms'], 'verified': d['verified']}))" $O/tmp.json $v | tee -a $O/ab.jsonl
   done
 done

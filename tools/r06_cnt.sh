@@ -14,7 +14,7 @@ timeout -k 10 600 $PYT tests/test_gpu_configs.py -k "two_lane or imix or random"
 tail -1 $O/tests.log
 run() {  # name lib args...
   local name=$1 lib=$2; shift 2
-  WG_LIB_PATH=$lib timeout -k 10 300 python bench.py --no-cpu-baseline --workload imix "$@" > $O/tmp.json 2>> $O/bench.err || die "bench $name" $?
+  WG_LIB_PATH=$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --workload imix "$@" > $O/tmp.json 2>> $O/bench.err || die "bench $name" $?
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(json.dumps({'variant': sys.argv[2], 'value': d['value'], 'ms_per_step': d['ms_per_step'], 'kernel_ms': d['roofline']['kernel_ms'], 'verified': d['verified']}))" $O/tmp.json "$name" >> $O/ab.jsonl
   tail -1 $O/ab.jsonl
 }
@@ -29,7 +29,7 @@ done
 cd /tmp && export TMPDIR=/tmp
 for v in stride16:$P stride1:$S; do
   n=${v%%:*}; lib=${v#*:}
-  WG_LIB_PATH=$lib timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_$n -o run --output-format csv -- python3 $ROOT/bench.py --workload imix --graph --no-cpu-baseline > $O/prof_bench_$n.json 2> $O/prof_$n.log || die prof_$n $?
+  WG_LIB_PATH=$lib timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_$n -o run --output-format csv -- python3 $ROOT/bench.py --full --workload imix --graph --no-cpu-baseline > $O/prof_bench_$n.json 2> $O/prof_$n.log || die prof_$n $?
   python3 $ROOT/tools/prof_window.py trace $(find $O/prof_$n -name "run_kernel_trace.csv" | head -1) $O/prof_bench_$n.json --out $O/window_$n.json > /dev/null || die window_$n $?
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], {k: d.get(k) for k in ('window_span_per_step_us', 'kernel_busy_per_step_us', 'planning_busy_per_step_us', 'gap_per_step_us')})" $O/window_$n.json $n
 done

@@ -12,7 +12,7 @@ cd $ROOT
 die() { echo "[final] FAILED: $1 (rc $2)"; exit $2; }
 run() {  # name -- args
   local name=$1; shift; shift
-  timeout -k 10 300 python bench.py "$@" > $O/$name.json 2>> $O/bench.err || die "bench $name" $?
+  timeout -k 10 300 python bench.py --full "$@" > $O/$name.json 2>> $O/bench.err || die "bench $name" $?
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(json.dumps({'variant': sys.argv[2], 'value': d['value'], 'ms_per_step': d['ms_per_step'], 'kernel_ms': d['roofline']['kernel_ms'], 'frac': d['roofline']['frac'], 'verified': d['verified']}))" $O/$name.json "$name" >> $O/ab.jsonl
   tail -1 $O/ab.jsonl
 }

@@ -16,7 +16,7 @@ tail -1 $O/tests.log
 for a in $(seq 1 $ALT); do
   for w in ${WL:-imix c2}; do
     for f in 1 0; do
-      WG_LPT_FUSED=$f timeout -k 10 300 python bench.py --no-cpu-baseline --workload $w > $O/tmp.json 2>> $O/bench.err || die "bench $w $f" $?
+      WG_LPT_FUSED=$f timeout -k 10 300 python bench.py --full --no-cpu-baseline --workload $w > $O/tmp.json 2>> $O/bench.err || die "bench $w $f" $?
       python3 - "$w" "$f" $O/tmp.json >> $O/ab.jsonl <<'PY'
 import json, sys
 d = json.load(open(sys.argv[3]))

@@ -6,7 +6,7 @@ mkdir -p $O
 die() { echo "[g] FAILED: $1 (rc $2)"; exit $2; }
 run() {
   local name=$1; shift
-  timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > $O/tmp.json 2>> $O/err.log || die "$name" $?
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > $O/tmp.json 2>> $O/err.log || die "$name" $?
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(json.dumps({'variant': sys.argv[2], 'value': d['value'], 'ms_per_step': d['ms_per_step'], 'host_enqueue_ms_per_step': d['host_enqueue_ms_per_step'], 'verified': d['verified']}))" $O/tmp.json "$name" >> $O/ab.jsonl
   tail -1 $O/ab.jsonl
 }

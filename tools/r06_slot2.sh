@@ -15,7 +15,7 @@ timeout -k 10 600 $PYT tests/test_gpu_configs.py -k "two_lane or imix" > $O/test
 tail -1 $O/tests.log
 for a in $(seq 1 $ALT); do
   for k in 0 1 2; do
-    WG_SLOT2=$k timeout -k 10 300 python bench.py --no-cpu-baseline --workload imix > $O/tmp.json 2>> $O/bench.err || die "bench $k" $?
+    WG_SLOT2=$k timeout -k 10 300 python bench.py --full --no-cpu-baseline --workload imix > $O/tmp.json 2>> $O/bench.err || die "bench $k" $?
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(json.dumps({'slot2': $k, 'value': d['value'], 'ms_per_step': d['ms_per_step'], 'kernel_ms': d['roofline']['kernel_ms'], 'verified': d['verified']}))" $O/tmp.json >> $O/ab.jsonl
     tail -1 $O/ab.jsonl
   done

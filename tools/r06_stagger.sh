@@ -20,21 +20,21 @@ PY
   tail -1 $O/ab.jsonl
 }
 for a in $(seq 1 $ALT); do
-  timeout -k 10 120 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/tmp.json 2>> $O/err.log || die stagger $?
+  timeout -k 10 120 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/tmp.json 2>> $O/err.log || die stagger $?
   line stagger20
-  timeout -k 10 120 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --stagger 0 > $O/tmp.json 2>> $O/err.log || die nostagger $?
+  timeout -k 10 120 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --stagger 0 > $O/tmp.json 2>> $O/err.log || die nostagger $?
   line nostagger20
 done
 for a in 1 2; do
-  timeout -k 10 120 python bench.py --no-cpu-baseline > $O/tmp.json 2>> $O/err.log || die stagger200 $?
+  timeout -k 10 120 python bench.py --full --no-cpu-baseline > $O/tmp.json 2>> $O/err.log || die stagger200 $?
   line stagger200
-  timeout -k 10 120 python bench.py --no-cpu-baseline --stagger 0 > $O/tmp.json 2>> $O/err.log || die nostagger200 $?
+  timeout -k 10 120 python bench.py --full --no-cpu-baseline --stagger 0 > $O/tmp.json 2>> $O/err.log || die nostagger200 $?
   line nostagger200
 done
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace -d $O/tr20 -o run --output-format csv -- python3 $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/tr20.json 2> $O/tr20.log || die trace20 $?
+timeout -k 10 300 rocprofv3 --kernel-trace -d $O/tr20 -o run --output-format csv -- python3 $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/tr20.json 2> $O/tr20.log || die trace20 $?
 python3 $ROOT/tools/stream_phase.py $(find $O/tr20 -name "run_kernel_trace.csv" | head -1) $O/tr20.json --out $O/phase_20.json || die phase20 $?
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trimix -o run --output-format csv -- python3 $ROOT/bench.py --workload imix --no-cpu-baseline > $O/trimix.json 2> $O/trimix.log || die traceimix $?
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trimix -o run --output-format csv -- python3 $ROOT/bench.py --full --workload imix --no-cpu-baseline > $O/trimix.json 2> $O/trimix.log || die traceimix $?
 python3 $ROOT/tools/prof_window.py trace $(find $O/trimix -name "run_kernel_trace.csv" | head -1) $O/trimix.json --out $O/window_imix.json || die windowimix $?
 python3 $ROOT/tools/trace_gaps.py $(find $O/trimix -name "run_kernel_trace.csv" | head -1) > $O/imix_gaps.txt || die gaps $?; cat $O/imix_gaps.txt
 echo "[stagger] done"

@@ -18,7 +18,7 @@ run() {  # name env... -- args
   local envs=()
   while [ "$1" != "--" ]; do envs+=("$1"); shift; done
   shift
-  env "${envs[@]}" timeout -k 10 300 python bench.py --no-cpu-baseline --workload imix "$@" > $O/tmp.json 2>> $O/bench.err || die "bench $name" $?
+  env "${envs[@]}" timeout -k 10 300 python bench.py --full --no-cpu-baseline --workload imix "$@" > $O/tmp.json 2>> $O/bench.err || die "bench $name" $?
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(json.dumps({'variant': sys.argv[2], 'value': d['value'], 'ms_per_step': d['ms_per_step'], 'kernel_ms': d['roofline']['kernel_ms'], 'verified': d['verified'], 'n_streams': d['config'].get('streams')}))" $O/tmp.json "$name" >> $O/ab.jsonl
   tail -1 $O/ab.jsonl
 }

@@ -10,13 +10,13 @@ tail -1 $O/tests.log
 for a in 1 2 3; do
   for w in imix c2; do
     for v in 1 0; do
-      WG_WS_EXT=$v timeout -k 10 300 python bench.py --no-cpu-baseline --workload $w > $O/tmp.json 2>> $O/bench.err || die "bench $w $v" $?
+      WG_WS_EXT=$v timeout -k 10 300 python bench.py --full --no-cpu-baseline --workload $w > $O/tmp.json 2>> $O/bench.err || die "bench $w $v" $?
       python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(json.dumps({'workload': sys.argv[2], 'ws_ext': int(sys.argv[3]), 'value': d['value'], 'ms_per_step': d['ms_per_step'], 'verified': d['verified']}))" $O/tmp.json $w $v | tee -a $O/ab.jsonl
     done
   done
 done
 for v in 1 0; do
-  WG_WS_EXT=$v timeout -k 10 300 python bench.py --no-cpu-baseline --workload imix --streams 2 > $O/tmp.json 2>> $O/bench.err || die "bench s2 $v" $?
+  WG_WS_EXT=$v timeout -k 10 300 python bench.py --full --no-cpu-baseline --workload imix --streams 2 > $O/tmp.json 2>> $O/bench.err || die "bench s2 $v" $?
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(json.dumps({'workload': 'imix --streams 2', 'ws_ext': int(sys.argv[2]), 'value': d['value'], 'ms_per_step': d['ms_per_step'], 'verified': d['verified']}))" $O/tmp.json $v | tee -a $O/ab.jsonl
 done
 echo "[wsext] done"

@@ -12,11 +12,11 @@ for rep in 1 2; do
   for w in imix; do
     for v in 0 planned all4; do
       case $v in 0) env="WG_SLOT4=0" ;; planned) env="WG_SLOT4_PLANNED=1" ;; all4) env="WG_SLOT4=1" ;; esac
-      line=$(env $env timeout -k 10 200 python bench.py --workload $w --no-cpu-baseline --steps 100 2>> $O/slot4_ab.err) || { echo "[slot4] bench FAILED $w $v"; exit 1; }
+      line=$(env $env timeout -k 10 200 python bench.py --full --workload $w --no-cpu-baseline --steps 100 2>> $O/slot4_ab.err) || { echo "[slot4] bench FAILED $w $v"; exit 1; }
       echo "$line" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(json.dumps({'workload':'$w','slot4':'$v','rep':$rep,'gib_s':d['value'],'kernel_ms':d['roofline']['kernel_ms'],'verified':d['verified']}))" | tee -a $O/slot4_ab.jsonl
     done
   done
 done
 echo "[slot4] c1"
-timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_c1.json 2>> $O/slot4_ab.err || exit 1
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_c1.json 2>> $O/slot4_ab.err || exit 1
 python3 -c "import json; d=json.load(open('$O/bench_c1.json')); print('c1', d['value'], d['verified'])"
