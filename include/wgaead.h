@@ -345,6 +345,91 @@ int wg_replay_state(wg_ctx* ctx, uint32_t slot, uint64_t* top, uint64_t* bits, u
 int wg_rx_check(wg_ctx* ctx, const wg_pkt* desc_dev, uint32_t n, const uint8_t* pt_dev, uint64_t pt_size,
                 uint32_t* status_dev, uint32_t flags, void* stream);
 
+/* ---- transmit side before seal: peer selection, send counters, wire slots ----
+ * The device counterpart of the reference's outbound path for a whole tun ring:
+ * which peers get a tun packet (PeerList.broadcastPacketToPeers, PeerList.java:94-106, hands every
+ * packet to every peer; TransportManager.sendOutgoingTransportNow, TransportManager.java:137-147,
+ * drops it for a peer without a session), the send counter (SymmetricKeypair.cipher claims it with
+ * SEND_COUNTER.getAndAdd(1), starting at 0 for a new keypair, SymmetricKeypair.java:37,:64;
+ * EncryptedOutgoingTransport.java:11-14 writes it into the header) and where the wire packet goes
+ * (UnencryptedOutgoingTransport.java:14-27: the header, then ct || tag at +16). wg_tx_plan writes the
+ * wg_pkt descriptors that wg_seal_batch(..., WG_F_FRAME) takes, so a tun ring becomes a UDP ring
+ * without per-packet host work, and the per-session send counters live where the nonces are built.
+ * Never claim counters for one session both here and on the host (SymmetricKeypair.claimCounters).
+ *
+ * wg_tx_plan(ctx, b, stream): tun packet t is in[pkt_off[t] .. +pkt_len[t]); wire slot j is
+ *   [wire_base + j * wire_stride, + wire_stride) of the seal's output buffer of out_size bytes.
+ *   Packet t passes the size checks if pkt_len <= max_len, pkt_off + pkt_len <= in_size,
+ *   pkt_len + 32 <= wire_stride and its last wire slot ends within out_size; otherwise its
+ *   descriptors get WG_PKT_TOOLONG. pkt_len = 0 passes: a keepalive (KeepaliveSender.java:39).
+ *   WG_TX_BROADCAST: n_desc = n * n_peers; descriptor j = t * n_peers + p is {in_off = pkt_off[t],
+ *     out_off = wire_base + j * wire_stride + 16, len = pkt_len[t], key_slot = peers[p], counter =
+ *     send[peers[p]] + r}, r = the number of packets before t in the batch that pass the size checks;
+ *     tx_status[j] = WG_PKT_OK. Afterwards send[peers[p]] += the number of packets that passed.
+ *   WG_TX_ROUTE: n_desc = n, j = t. A packet that passes the size checks is routed by its
+ *     destination address, read as destinationIPOf reads it (TransportManager.java:124-130: version
+ *     nibble 4: bytes 16..19, nibble 6: bytes 24..39): another nibble, or a packet that ends before
+ *     the address does (a keepalive too), gets WG_PKT_BADIP; no prefix of wg_routes_set covering the
+ *     address, WG_PKT_NOROUTE. A routed packet gets the key slot of the longest matching prefix,
+ *     status WG_PKT_OK and counter = send[slot] + the number of routed packets to the same slot with
+ *     a lower batch index; every slot then advances by its count, so counters stay dense per slot,
+ *     a peer sees them in the order its packets were read, and two runs from one state give the same
+ *     bytes.
+ *   Every one of the n_desc descriptors and statuses is written. A descriptor whose status is not
+ *   WG_PKT_OK has len = WG_LEN_INVALID (the seal and the framer skip it and leave its wire slot
+ *   untouched), counter 0, in_off and out_off as above (modulo 2^64) and key_slot = peers[p]
+ *   (broadcast) or 0 (route); it consumes no counter. Counters are 64-bit and wrap like a Java long.
+ *   desc_out: 16-byte aligned. n_desc must stay below 2^31. n = 0, or no peers, writes nothing.
+ *   Asynchronous on `stream`; run wg_seal_batch(desc_out, n_desc, ..., WG_F_FRAME) on the same stream.
+ *   Plans on different streams of one context are ordered by the library (they share the counters
+ *   and the scratch). Graphs: a plan may be captured (after wg_tx_reserve: a capturing stream cannot
+ *   allocate, WG_EINVAL) and replayed any number of times; each replay continues the counters. The
+ *   peer list, the route table header and the counters have fixed device addresses for the life of
+ *   the context, so wg_routes_set, wg_tx_counters_set and a wg_tx_peers_set with the SAME number of
+ *   peers need no re-capture (another number of peers changes n_desc: capture again). The library
+ *   does not order a graph launch against eager plans on other streams: the caller does.
+ * wg_tx_peers_set: the peers of broadcast mode as key slots, in PeerList iteration order; list only
+ *   peers with a session. A slot >= the key table is WG_ERANGE, a repeated slot WG_EINVAL (it would
+ *   use every nonce twice). Synchronous, like wg_keys_set.
+ * wg_routes_set: replaces the whole cryptokey-routing table (n = 0 clears it): prefix k routes to
+ *   key_slots_host[k]. Standard longest-prefix match: a prefix of length L matches an address whose
+ *   first L bits equal it, so /0, /32 and /128 entries match; of equal prefixes the later entry
+ *   wins. This is NOT IPFilter.search's rule (wg_filter_set), under which a full-length entry never
+ *   matches: the reference has no outbound routing (it broadcasts), so there is nothing to be
+ *   faithful to, and WireGuard's cryptokey routing is plain longest-prefix match. Synchronous.
+ * wg_tx_counters_set / wg_tx_counters_get: the send counters of slots [first_slot, first_slot + n),
+ *   ordered after every plan queued before the call (get waits for them). Counters are zero at
+ *   creation; wg_keys_set / wg_keys_zero zero the counters of the slots they touch (a new
+ *   SymmetricKeypair starts at 0), ordered after every plan queued before them.
+ * wg_tx_reserve: scratch for plans of up to max_packets tun packets (either mode). A plan that needs
+ *   more allocates it, except on a capturing stream. The counters and the scratch are allocated at
+ *   the first wg_tx_* call: a context that never plans pays nothing. */
+#define WG_PKT_NOROUTE 8u   /* route mode: no prefix covers the destination */
+#define WG_PKT_TOOLONG 9u   /* len > max_len, packet overruns in_size, or its wire slot overruns stride / out_size */
+#define WG_TX_BROADCAST 0u
+#define WG_TX_ROUTE 1u
+typedef struct wg_tx_batch {
+  const uint8_t* in;       /* tun ring (device) */
+  uint64_t in_size;
+  const uint64_t* pkt_off; /* device, n entries */
+  const uint32_t* pkt_len; /* device, n entries */
+  wg_pkt* desc_out;        /* device, 16-byte aligned, n_desc entries */
+  uint32_t* tx_status;     /* device, n_desc entries, WG_PKT_* */
+  uint64_t wire_base;
+  uint64_t wire_stride;
+  uint64_t out_size;
+  uint32_t n;
+  uint32_t max_len;
+  uint32_t mode;           /* WG_TX_BROADCAST or WG_TX_ROUTE */
+  uint32_t _reserved;
+} wg_tx_batch;
+int wg_tx_peers_set(wg_ctx* ctx, const uint32_t* key_slots_host, uint32_t n);
+int wg_routes_set(wg_ctx* ctx, const wg_prefix* prefixes, const uint32_t* key_slots_host, uint32_t n);
+int wg_tx_counters_set(wg_ctx* ctx, uint32_t first_slot, uint32_t n, const uint64_t* counters_host);
+int wg_tx_counters_get(wg_ctx* ctx, uint32_t first_slot, uint32_t n, uint64_t* counters_host);
+int wg_tx_reserve(wg_ctx* ctx, uint32_t max_packets);
+int wg_tx_plan(wg_ctx* ctx, const wg_tx_batch* batch, void* stream);
+
 int wg_seal1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* pt, uint32_t len, uint8_t* out);
 int wg_open1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* in, uint32_t len, uint8_t* pt);
 int wg_pp_config(wg_ctx* ctx, uint32_t waves, uint32_t idle_us);

@@ -30,10 +30,14 @@ WG_PKT_BADIP = 4
 WG_PKT_FILTERED = 5
 WG_PKT_REPLAY = 6
 WG_PKT_NOKEY = 7
+WG_PKT_NOROUTE = 8
+WG_PKT_TOOLONG = 9
 WG_PKT_FAILED = 255
 WG_QUEUE_MAX_LEN = 16384
 WG_RX_FILTER = 1
 WG_RX_REPLAY = 2
+WG_TX_BROADCAST = 0
+WG_TX_ROUTE = 1
 WG_MAX_FILTERS = 65536
 WG_NO_FILTER = 0xFFFFFFFF
 WG_LEN_INVALID = 0xFFFFFFFF
@@ -83,6 +87,15 @@ class WgBatch(ctypes.Structure):
                 ("_reserved", ctypes.c_uint32)]
 
 
+class WgTxBatch(ctypes.Structure):
+    """wg_tx_batch: one wg_tx_plan call (device pointers)."""
+    _fields_ = [("in_", ctypes.c_void_p), ("in_size", ctypes.c_uint64), ("pkt_off", ctypes.c_void_p),
+                ("pkt_len", ctypes.c_void_p), ("desc_out", ctypes.c_void_p), ("tx_status", ctypes.c_void_p),
+                ("wire_base", ctypes.c_uint64), ("wire_stride", ctypes.c_uint64), ("out_size", ctypes.c_uint64),
+                ("n", ctypes.c_uint32), ("max_len", ctypes.c_uint32), ("mode", ctypes.c_uint32),
+                ("_reserved", ctypes.c_uint32)]
+
+
 class WgCompletion(ctypes.Structure):
     """wg_completion: one reaped packet of a wg_queue."""
     _fields_ = [("user", ctypes.c_uint64), ("counter", ctypes.c_uint64), ("data", ctypes.c_void_p),
@@ -97,6 +110,7 @@ class WgSubmit(ctypes.Structure):
 
 
 assert ctypes.sizeof(WgBatch) == 64 and ctypes.sizeof(WgCompletion) == 48 and ctypes.sizeof(WgSubmit) == 32
+assert ctypes.sizeof(WgTxBatch) == 88
 assert ctypes.sizeof(WgPkt) == 32 and ctypes.sizeof(WgAeadDesc) == 64 and ctypes.sizeof(WgPrefix) == 18
 
 # (name, restype, argtypes) for every symbol include/wgaead.h declares
@@ -128,6 +142,12 @@ SIGNATURES = [
     ("wg_replay_reset", _I, [_VP, _U32, _U32]),
     ("wg_replay_state", _I, [_VP, _U32, ctypes.POINTER(_U64), _VP, _U32]),
     ("wg_rx_check", _I, [_VP, _VP, _U32, _VP, _U64, _VP, _U32, _VP]),
+    ("wg_tx_peers_set", _I, [_VP, _VP, _U32]),
+    ("wg_routes_set", _I, [_VP, _VP, _VP, _U32]),
+    ("wg_tx_counters_set", _I, [_VP, _U32, _U32, _VP]),
+    ("wg_tx_counters_get", _I, [_VP, _U32, _U32, _VP]),
+    ("wg_tx_reserve", _I, [_VP, _U32]),
+    ("wg_tx_plan", _I, [_VP, ctypes.POINTER(WgTxBatch), _VP]),
     ("wg_seal1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_open1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_pp_config", _I, [_VP, _U32, _U32]),

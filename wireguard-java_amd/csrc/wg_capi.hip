@@ -93,6 +93,7 @@ struct PPServer;  // wg_pp.hip
 void pp_stop(wg_ctx* c);
 int rx_tables(wg_ctx* c, const wgt::RxTables** out);  // wg_rx.hip
 struct RxState;  // wg_rx.hip
+struct TxState;  // wg_tx.hip
 
 }  // namespace
 
@@ -193,6 +194,7 @@ struct wg_ctx {
   std::unique_ptr<std::atomic<uint32_t>[]> key_live;
   std::mutex keys_mu;
   RxState* rx = nullptr;  // receive-side checks (wg_rx.hip)
+  TxState* tx = nullptr;  // transmit-side planning: send counters, peers, routes (wg_tx.hip)
   // timing
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -898,6 +900,7 @@ int launch_after_seal(wg_ctx* c, const wg_batch* sb, const wg_batch* ob, hipStre
 }  // namespace
 
 #include "wg_rx.hip"
+#include "wg_tx.hip"
 
 extern "C" {
 
@@ -1026,6 +1029,7 @@ int wg_ctx_destroy(wg_ctx* c) {
   }
   DeviceGuard g(c->device);
   rx_free(c);
+  tx_free(c);
   if (c->keys) {
     (void)hipDeviceSynchronize();  // no launch of this context may still read the table
     (void)hipMemsetAsync(c->keys, 0, (size_t)c->key_slots * 32, c->stream);  // SymmetricKeypair.clean zeroes keys
@@ -1079,6 +1083,7 @@ int wg_keys_set(wg_ctx* c, uint32_t first, uint32_t n, const uint8_t* keys_host)
   }
   int rc;
   if ((rc = rx_reset_slots(c, first, n, c->stream)) != WG_OK) return rc;  // new key: new session
+  if ((rc = tx_reset_slots(c, first, n, c->stream)) != WG_OK) return rc;  // ... whose send counter starts at 0
   HIPTRY(hipStreamSynchronize(c->stream));
   return WG_OK;
 }
@@ -1096,6 +1101,7 @@ int wg_keys_zero(wg_ctx* c, uint32_t first, uint32_t n) {
   }
   int rc;
   if ((rc = rx_reset_slots(c, first, n, c->stream)) != WG_OK) return rc;
+  if ((rc = tx_reset_slots(c, first, n, c->stream)) != WG_OK) return rc;
   HIPTRY(hipStreamSynchronize(c->stream));
   return WG_OK;
 }

@@ -217,6 +217,64 @@ class Engine:
         L.check(self._lib.wg_rx_check(self.ctx, desc.data_ptr(), n, pt.data_ptr(), pt.numel(), status.data_ptr(),
                                       flags, stream if stream is not None else _torch_stream()))
 
+    # ---- transmit side before seal (wg_tx_plan) ---------------------------------------
+    def tx_peers_set(self, key_slots) -> None:
+        """wg_tx_peers_set: the peers of broadcast mode as key slots, in PeerList iteration order
+        (PeerList.java:94-106); list only peers with a session."""
+        ids = np.ascontiguousarray(np.asarray(key_slots, dtype=np.uint32))
+        L.check(self._lib.wg_tx_peers_set(self.ctx, ids.ctypes.data, len(ids)))
+
+    def routes_set(self, routes) -> None:
+        """wg_routes_set: the whole cryptokey-routing table from (address string or ipaddress
+        object, prefix_len, key_slot) triples; longest prefix wins, of equal prefixes the later."""
+        import ipaddress
+        arr = (L.WgPrefix * max(1, len(routes)))()
+        slots = np.zeros(max(1, len(routes)), np.uint32)
+        for k, (addr, plen, slot) in enumerate(routes):
+            a = ipaddress.ip_address(addr) if isinstance(addr, str) else addr
+            arr[k].family = 4 if a.version == 4 else 6
+            arr[k].prefix_len = plen
+            for i, x in enumerate(a.packed):
+                arr[k].addr[i] = x
+            slots[k] = slot
+        L.check(self._lib.wg_routes_set(self.ctx, ctypes.addressof(arr), slots.ctypes.data, len(routes)))
+
+    def tx_counters_set(self, first_slot: int, counters) -> None:
+        """wg_tx_counters_set: the send counters of slots [first_slot, first_slot + len(counters))."""
+        v = np.ascontiguousarray(np.asarray(counters, dtype=np.uint64))
+        L.check(self._lib.wg_tx_counters_set(self.ctx, first_slot, len(v), v.ctypes.data))
+
+    def tx_counters_get(self, first_slot: int, n: int) -> np.ndarray:
+        """wg_tx_counters_get: the send counters after every plan queued so far (uint64 array)."""
+        v = np.zeros(max(n, 1), np.uint64)
+        L.check(self._lib.wg_tx_counters_get(self.ctx, first_slot, n, v.ctypes.data))
+        return v[:n]
+
+    def tx_reserve(self, max_packets: int) -> None:
+        """wg_tx_reserve: scratch for plans of up to max_packets tun packets (needed before a plan
+        is captured into a graph: a capturing stream cannot allocate)."""
+        L.check(self._lib.wg_tx_reserve(self.ctx, max_packets))
+
+    def tx_plan(self, tun, pkt_off, pkt_len, desc_out, tx_status, wire_stride: int, out_size: int, max_len: int,
+                route: bool = False, wire_base: int = 0, stream: int | None = None) -> None:
+        """wg_tx_plan over torch tensors: tun uint8 ring, pkt_off int64 [n], pkt_len int32 [n],
+        desc_out int64 [n_desc, 4] (wg_pkt records for seal()), tx_status int32 [n_desc]; n_desc = n in
+        route mode, n x peers in broadcast mode. Wire slot j is out[wire_base + j * wire_stride ...) of the
+        seal's output buffer of out_size bytes; the send counters live on the device."""
+        b = L.WgTxBatch(tun.data_ptr(), tun.numel(), pkt_off.data_ptr(), pkt_len.data_ptr(), desc_out.data_ptr(),
+                        tx_status.data_ptr(), wire_base, wire_stride, out_size, pkt_off.shape[0], max_len,
+                        L.WG_TX_ROUTE if route else L.WG_TX_BROADCAST, 0)
+        L.check(self._lib.wg_tx_plan(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def tx_seal(self, tun, pkt_off, pkt_len, desc_out, tx_status, out, wire_stride: int, max_len: int,
+                route: bool = False, wire_base: int = 0, uniform: bool = False, stream: int | None = None) -> None:
+        """tun ring -> UDP ring on one stream: tx_plan, then seal(desc_out, tun, out, frame=True). The
+        receiver table (set_receivers) must be set; packets the plan rejects leave their wire slot untouched."""
+        st = stream if stream is not None else _torch_stream()
+        self.tx_plan(tun, pkt_off, pkt_len, desc_out, tx_status, wire_stride, out.numel(), max_len, route=route,
+                     wire_base=wire_base, stream=st)
+        self.seal(desc_out, tun, out, max_len, uniform=uniform, stream=st, frame=True)
+
     def set_receivers(self, receivers) -> None:
         """wg_ctx_set_receivers: device tensor of receiver_index per key slot for
         seal(..., frame=True) — contiguous, 4-byte integers, on this engine's device, at

@@ -15,6 +15,12 @@ import static java.lang.foreign.ValueLayout.*;
  * {in_off u64, out_off u64, counter u64, len u32, key_slot u32} over one input
  * and one output buffer; seal writes ct || tag at out_off, open verifies then
  * writes pt (status[i] = 1 and a zeroed pt for a forged packet).
+ *
+ * Send counters: a host-built seal table takes each packet's counter from
+ * {@code SymmetricKeypair.claimCounters}; a table planned on the device
+ * ({@code WgAead.TX_PLAN}, wg_tx_plan: peers or routes, counters and wire slots for a
+ * whole tun ring) takes it from the device's per-slot send counters. The two are
+ * alternatives: never use both for one session, or a nonce is used twice.
  */
 public final class TransportBatch {
 	private TransportBatch() {}

@@ -33,13 +33,16 @@ public final class WgAead {
 	/** wg_rx_check outcomes (TransportManager.processDecryptedTransport, TransportManager.java:98-119). */
 	public static final int WG_PKT_KEEPALIVE = 3, WG_PKT_BADIP = 4, WG_PKT_FILTERED = 5, WG_PKT_REPLAY = 6;
 	public static final int WG_RX_FILTER = 1, WG_RX_REPLAY = 2, WG_NO_FILTER = -1;
-	public static final long AEAD_DESC_SIZE = 64, PKT_DESC_SIZE = 32, BATCH_SIZE = 64;
+	/** wg_tx_plan outcomes beside WG_PKT_OK / WG_PKT_BADIP: no route covers the destination; the packet or its wire slot does not fit. */
+	public static final int WG_PKT_NOROUTE = 8, WG_PKT_TOOLONG = 9;
+	public static final int WG_TX_BROADCAST = 0, WG_TX_ROUTE = 1;
+	public static final long AEAD_DESC_SIZE = 64, PKT_DESC_SIZE = 32, BATCH_SIZE = 64, TX_BATCH_SIZE = 88;
 
 	static final MethodHandle SELFTEST, CTX_CREATE, LAST_ERROR, KEYS_SET, KEYS_ZERO, SEAL1, OPEN1, AEAD_HOST,
 		SEAL_BATCH, OPEN_BATCH, SYNC, SEAL_HOST, OPEN_HOST, HOST_ALLOC, HOST_FREE, FRAME_SEAL, PARSE_OPEN,
 		FILTER_SET, SLOT_FILTERS_SET, REPLAY_ENABLE, REPLAY_RESET, RX_CHECK, DUPLEX_BATCH, QUEUE_CREATE,
 		QUEUE_DESTROY, SUBMIT_SEAL, SUBMIT_OPEN, SUBMIT_SEAL_N, SUBMIT_OPEN_N, REAP, REAP_DONE, QUEUE_SUBMIT_TIMEOUT,
-		NUMA_NODE;
+		NUMA_NODE, TX_PEERS_SET, ROUTES_SET, TX_COUNTERS_SET, TX_COUNTERS_GET, TX_RESERVE, TX_PLAN;
 
 	/** The process-wide context (one HIP device, its stream and its device key table). */
 	static final MemorySegment CTX;
@@ -87,6 +90,19 @@ public final class WgAead {
 			JAVA_INT));
 		RX_CHECK = down(linker, symbols, "wg_rx_check", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT,
 			ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS));
+		// transmit side before seal: peers / routes, device send counters, wire slots (PeerList.java:94-106,
+		// SymmetricKeypair.java:37,:64, UnencryptedOutgoingTransport.java:14-27); wg_tx_plan takes one
+		// wg_tx_batch struct of 88 bytes
+		TX_PEERS_SET = down(linker, symbols, "wg_tx_peers_set", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS,
+			JAVA_INT));
+		ROUTES_SET = down(linker, symbols, "wg_routes_set", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS,
+			JAVA_INT));
+		TX_COUNTERS_SET = down(linker, symbols, "wg_tx_counters_set", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT,
+			JAVA_INT, ADDRESS));
+		TX_COUNTERS_GET = down(linker, symbols, "wg_tx_counters_get", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT,
+			JAVA_INT, ADDRESS));
+		TX_RESERVE = down(linker, symbols, "wg_tx_reserve", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT));
+		TX_PLAN = down(linker, symbols, "wg_tx_plan", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
 		// outgoing seal + incoming open in one launch (two wg_batch structs of 64 bytes)
 		DUPLEX_BATCH = down(linker, symbols, "wg_duplex_batch", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS,
 			ADDRESS));
