@@ -96,6 +96,13 @@ def test_fault_hooks_only_in_the_test_library():
     t = open(test_lib, "rb").read()
     for hook in (b"WG_TEST_STEP_FLIP", b"WG_RX_TEST_SKEW", b"WG_RX_TEST_MUTANT"):
         assert hook in t, hook
+    # the A/B variants that lost (docs/EXPERIMENTS.md) and the knobs folded to their defaults are in neither
+    # library: no stray variable can select a kernel that only an A/B run ever exercised
+    for gone in (b"WG_STITCH", b"WG_CLAIM", b"WG_LPT_FUSED", b"WG_LPT_WIDE", b"WG_FUSED_POLL", b"WG_FUSED_NP",
+                 b"WG_SLOT4_PAIRS", b"WG_SLOT4_SNAKE", b"WG_STEP_WPE4", b"WG_WS_EXT", b"WG_WSEV",
+                 b"k_step_claim", b"k_step_mixed_fused"):
+        assert gone not in prod, gone
+        assert gone not in t, gone
 
 
 def test_no_key_codes_declared():

@@ -146,15 +146,11 @@ def test_plain_run_is_lean_and_dumps_the_last_steps_outputs(tmp_path):
     assert np.array_equal(ref.reshape(p, stride)[:, :L + 16], ct[:, :L + 16])
 
 
-def test_bench_imix_fused_planning_is_verified():
-    """WG_LPT_FUSED=1 (A/B knob, off by default): the IMIX step's short-packet plan made by the step launch's
-    own first workgroups (k_step_mixed_fused) while the others wait on its publication count, with each poll
-    kind (WG_FUSED_POLL 0/1/2) and planner count (WG_FUSED_NP): every packet must still round-trip and the
-    oracle sample be bit-exact, as on the default two-launch plan."""
-    for env in ({}, {"WG_LPT_FUSED": "1"}, {"WG_LPT_FUSED": "1", "WG_FUSED_POLL": "2", "WG_FUSED_NP": "256"},
-                {"WG_LPT_FUSED": "1", "WG_FUSED_POLL": "1", "WG_FUSED_NP": "7"}):
-        rc, line = _bench(env, "3", "--workload", "imix")
-        assert rc == 0 and line["verified"] is True and line["oracle_sample"]["bit_exact"] is True, (env, line)
+def test_bench_imix_default_plan_is_verified():
+    """The IMIX bench line on the default plan (k_lpt_one's own launch, then the k_step_mixed step): every
+    packet must round-trip and the oracle sample be bit-exact."""
+    rc, line = _bench({}, "3", "--workload", "imix")
+    assert rc == 0 and line["verified"] is True and line["oracle_sample"]["bit_exact"] is True, line
 
 
 def test_bench_imix_two_streams_own_workspaces():

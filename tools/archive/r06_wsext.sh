@@ -1,4 +1,6 @@
 #!/bin/bash
+# ARCHIVED: the library no longer reads WG_WS_EXT (folded to its default, the stop event), so both arms of
+# this A/B now run the same code. Kept as the record of how profiles/r06_ws_ext_ab.jsonl was taken.
 # Round 6: the workspace event recorded by the step kernel's own completion (hipExtLaunchKernel stop event,
 # WG_WS_EXT) instead of a hipEventRecord after it: the GPU suite, then IMIX / C2 / C1 lines alternating.
 set -o pipefail

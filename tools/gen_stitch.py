@@ -27,6 +27,11 @@ Every instruction is an 8-byte encoding (VOP3 / DS), so the placed stream keeps 
 issue rate; each s_waitcnt is paired with an s_nop 0 (two 4-byte instructions).
 Step t reads its chunk at %39 + 4 G t (chunks c0 + G t of the slot, one row of the image).
 Horner step (poly_mul of wg_device.h, then the chunk's limbs added): acc' = acc R + m, carry-seeded chains.
+
+Status: the stitched kernels measured slower (docs/EXPERIMENTS.md) and were removed from the library, which no
+longer includes the header; commit 21f09fc is the last whose wg_transport.hip uses it. This generator, the
+header and their CPU tests (tests/test_stitch_asm.py, tests/test_stitch_schedule.py: seven tests) are left to be deleted
+together in a change of their own.
 """
 import os
 import sys

@@ -115,42 +115,19 @@ struct wg_ctx {
   // mixed batches of short packets (WG_SLOT4): -1 planned (16-lane slots for the long packets, 4-lane for the
   // rest), 0 never, 1 always 4-lane slots for every packet, 2 always the 16 / 4 split
   int slot4 = -1;
-  bool slot4_pairs = false;               // 4-lane slots in longest-first pairs even when one packet per slot fits (A/B)
-  bool slot4_snake = true;                // 4-lane slots: odd workgroup generations reversed (WG_SLOT4_SNAKE=0: not; A/B)
   uint32_t cus = 0;                       // compute units
   int prio_mode = -1;                     // progress-based issue priority: -1 mixed batches only, 0 off, 1 on (WG_PRIO)
   uint32_t uniform16 = 8;                 // uniform batches of n <= S8 / k packets in 16-lane slots (WG_UNIFORM16=k; 0 never)
   uint32_t mixed_split = 0;               // > 0: mixed batches one packet per slot, packets of more than this
                                           // many 8-block rounds in 16-lane slots (WG_MIXED_SPLIT)
   bool step_two_launches = false;         // wg_ctx_set_kernel variant 1: WG_F_AFTER_SEAL as seal + open launches
-  // half-occupancy k_step grids (C2's longest-first pairs) take the build allocated for 4 waves per
-  // SIMD: no SGPR spills, C2 +0.7% in 3 alternations (profiles/r04_wpe_ab.txt); WG_STEP_WPE4=0: not
-  bool step_wpe4 = true;
-  // mixed-length WG_F_AFTER_SEAL steps through k_step_claim (dynamic claims over the longest-first
-  // order) instead of the static snake (WG_CLAIM=1; A/B)
-  bool claim = false;
-  // WG_F_AFTER_SEAL steps with the stitched Horner (transport_body ST: a round's Horner steps interleaved
-  // into the next round's ChaCha20 rounds; WG_STITCH=0|1, A/B)
-  bool stitch = false;
   // the short-packet split plan's order in one launch (k_lpt_one; WG_LPT_ONE=0: k_lpt_hist + k_lpt_scatter)
   bool lpt_one = true;
-  // ... and for the 8-lane longest-first pairs of other mixed steps (C2; WG_LPT_WIDE=1, A/B): planning 9.9 ->
-  // 6.5 us per C2 step, but k_step 411.8 -> 416.5 us (19 round keys order less finely than the two launches'
-  // 130 bins, and the sparse lookups): C2 -0.3% (profiles/r06_lpt_wide_ab.jsonl); off
-  bool lpt_wide = false;
-  // WG_LPT_FUSED=1 (A/B, off): in a k_step_mixed step, planned by the step launch's first workgroups
-  // (k_step_mixed_fused) instead of k_lpt_one's own launch. IMIX 66-70 us per step against 59: the planners
-  // take 6-8 us while every other workgroup waits, more than the launch gap they remove
-  // (profiles/r06_fused_ab.jsonl). plan_err: a pinned word the fused kernel sets when a workgroup's wait for
-  // the plan ran out (a later step then fails with WG_EDEVICE)
-  bool lpt_fused = false;
   // the short-packet split plan's tiny packets (keys <= slot2, i.e. at most 8 x slot2 blocks: 448 B for 1) in
-  // 2-lane slots (k_step_mixed<4, false, 2>; WG_SLOT2=k, 0: none). IMIX +2.3% (715 -> 731 GiB/s, three
+  // 2-lane slots (k_step_mixed<4, 2>; WG_SLOT2=k, 0: none). IMIX +2.3% (715 -> 731 GiB/s, three
   // alternations); 65,536 x 40 B 37.0 -> 27.1 us per step; 2 (576-B packets too) measured +-0
   // (profiles/r06_slot2_ab.jsonl)
   uint32_t slot2 = 1;
-  uint32_t fused_poll = 0, fused_np = 0;  // WG_FUSED_POLL (k_step_mixed_fused's poll kind), WG_FUSED_NP (planners)
-  uint32_t* plan_err = nullptr;
   // test hook WG_TEST_STEP_FLIP=N (power of two): the k_step launch's seal half writes a wrong tag for every
   // packet whose index is a multiple of N (tests/test_gpu_bench.py: the bench must report verified false)
   uint32_t test_flip = 0;
@@ -158,7 +135,6 @@ struct wg_ctx {
   DevBuf plan_nb, plan_prefix, plan_tiles, plan_ntiles, plan_tmp, lpt_hist, lpt_order;
   DevBuf lpt_hist2, lpt_order2;  // the open half of a wg_duplex_batch
   DevBuf lpt_nlong;              // k_lpt_scatter -> k_*_mixed: long packets at the front of lpt_order
-  DevBuf lpt_claim, lpt_chain;   // k_step_claim: sub-order counters (64-B lines) and the seal half's per-position log
   // per-stream plan workspaces for the short-packet split plan's WG_F_AFTER_SEAL steps (k_lpt_one's counters
   // and sparse order): calls on different streams then plan and run concurrently instead of waiting for
   // each other's workspace (ws_acquire). Up to kStreamWS streams; each use waits for the workspace's last
@@ -172,8 +148,6 @@ struct wg_ctx {
   static constexpr size_t kStreamWS = 8;
   std::vector<std::unique_ptr<StreamWS>> stream_ws;
   bool stream_ws_on = true;
-  bool ws_ext = true;  // WG_WS_EXT=0: the workspace event as a hipEventRecord after the step launch (A/B)
-  uint32_t wsev = 3;  // WG_WSEV (A/B): bit 0 record an event after each use, bit 1 wait on it before the next
 
   int kern = KERN_TRANSPORT;
   // host-API staging
@@ -417,12 +391,8 @@ int plan_transport(wg_ctx* c, const wg_pkt* desc, uint32_t n, const uint8_t* in,
                    uint64_t out_size, uint32_t* status, uint32_t max_len, uint32_t flags, hipStream_t s,
                    uint64_t cap_waves, uint32_t G, DevBuf& lpt_hist, DevBuf& lpt_order, wgt::TransportParams* Pout,
                    uint32_t* grid_out, bool* ordered_out, const wgt::RxTables* rx = nullptr,
-                   bool private_ws = false, bool reuse_order = false, uint32_t split = 0,
-                   uint32_t* claim = nullptr, uint32_t claim_nc = 0, bool* defer_one = nullptr,
-                   bool wide_ok = false) {
+                   bool private_ws = false, bool reuse_order = false, uint32_t split = 0) {
   bool ordered = false;
-  const bool may_defer = defer_one && *defer_one;
-  if (defer_one) *defer_one = false;
   wgt::TransportParams P{};
   P.desc = desc;
   P.n = n;
@@ -452,8 +422,8 @@ int plan_transport(wg_ctx* c, const wg_pkt* desc, uint32_t n, const uint8_t* in,
   // packets: 4 per slot (4096 waves) 1,322 GiB/s, 2 per slot (8192 waves) 1,208, 3 per slot 1,148.
   if (!(flags & WG_F_UNIFORM) && 2ull * n > cap_slots) per_slot = 2 * ((n + cap_slots - 1) / cap_slots);
   // 4-lane slots (16 per wave) hold a 65,536-packet batch one packet per slot at 4 waves per SIMD; pairs
-  // would halve the waves (WG_SLOT4_PAIRS=1: pairs as for 8-lane slots, A/B)
-  if (G == 4 && !c->slot4_pairs && n <= cap_slots) per_slot = 1;
+  // would halve the waves
+  if (G == 4 && n <= cap_slots) per_slot = 1;
 #ifndef WG_PERSISTENT_UNIFORM
   // uniform lengths: one packet per slot and as many waves as that takes; the hardware
   // dispatcher starts each new wave as an old one retires, so a wave's packet-start
@@ -469,15 +439,7 @@ int plan_transport(wg_ctx* c, const wg_pkt* desc, uint32_t n, const uint8_t* in,
   // 4-lane slots, one packet each, longest first: all waves are resident at once, and wave w shares its
   // SIMD with waves w + 4 x CUs k; reversing every other generation of 4 x CUs waves deals each SIMD long
   // and short packets in turn (without it a SIMD holding the longest packets ran alone at the end)
-  if (G == 4 && per_slot == 1 && c->slot4_snake) P.wave_gen = wgt::TW * c->cus;
-  if (claim) {  // k_step_claim: the largest power of two <= claim_nc that divides the grid (every sub-order
-                // then has the same number of workgroups, and its static first positions end at claim_base)
-    uint32_t nc = claim_nc;
-    while (nc > 1 && grid % nc) nc >>= 1;
-    P.claim = claim;
-    P.claim_nc = nc;
-    P.claim_base = P.slots / nc;
-  }
+  if (G == 4 && per_slot == 1) P.wave_gen = wgt::TW * c->cus;
   // mixed lengths: the rounds a slot runs, spread over the 4 issue-priority levels (k_transport),
   // so the waves that have done the least work issue first (C2 +2%); uniform batches keep the
   // default oldest-first arbitration (the same schedule cost C1 2%)
@@ -494,17 +456,11 @@ int plan_transport(wg_ctx* c, const wg_pkt* desc, uint32_t n, const uint8_t* in,
     // private_ws: buffers owned by the caller's stream (no shared-workspace ordering)
     // one: the short-packet split plan orders in ONE launch (k_lpt_one: sparse order, double-buffered
     // counters, no memset) instead of k_lpt_hist + k_lpt_scatter (WG_LPT_ONE=0: the two launches, A/B)
-    // wide: the same one-launch plan over up to kWideBins keys for a k_step<8, 4> step of a mixed batch on
-    // the 8-lane longest-first pairs (C2; WG_LPT_WIDE=0: the two launches); wide_ok from launch_after_seal,
-    // and exactly the condition under which it launches k_step<8, 4> (the kernel that reads this order)
-    const uint32_t key_max = (((max_len + 63u) >> 6) + 1u + 7u) >> 3;
-    const bool wide = wide_ok && !mixed && !claim && c->lpt_one && c->lpt_wide && key_max < wgt::kWideBins &&
-                      G == 8 && c->step_wpe4 && 2ull * grid * wgt::TW <= cap_waves && !c->stitch && !c->test_flip;
-    const bool one = (mixed && max_len <= 2048u && !claim && c->lpt_one) || wide;
+    const bool one = mixed && max_len <= 2048u && c->lpt_one;
     if (!reuse_order && one) {
       int rc;
       if ((rc = lpt_hist.ensure(2 * wgt::kPlanSet * sizeof(uint32_t))) != WG_OK) return rc;
-      if ((rc = lpt_order.ensure(sizeof(uint32_t) * (wide ? wgt::kWideBins : wgt::kFastBins) * (size_t)n)) != WG_OK)
+      if ((rc = lpt_order.ensure(sizeof(uint32_t) * wgt::kFastBins * (size_t)n)) != WG_OK)
         return rc;
       if (!private_ws && (rc = ws_acquire(c, s)) != WG_OK) return rc;
       if (!lpt_hist.zeroed) {  // a new buffer, or one the two-launch planner wrote histograms into
@@ -515,19 +471,11 @@ int plan_transport(wg_ctx* c, const wg_pkt* desc, uint32_t n, const uint8_t* in,
       uint32_t* cnt = (uint32_t*)lpt_hist.p + wgt::kPlanSet * lpt_hist.par;
       uint32_t* nxt = (uint32_t*)lpt_hist.p + wgt::kPlanSet * (lpt_hist.par ^ 1u);
       const uint32_t lgrid = std::max<uint32_t>(1u, std::min<uint32_t>(wgt::LPT_MAX_BLOCKS, (n + 1023u) / 1024u));
-      if (may_defer && !wide) {  // the caller's k_step_mixed_fused launch plans (into cnt / nxt, as below)
-        *defer_one = true;
-      } else if (wide) {
-        hipLaunchKernelGGL((wgt::k_lpt_one<MODE, wgt::LPT_THREADS, 1, wgt::kWideBins>), dim3(lgrid),
-                           dim3(wgt::LPT_THREADS), 0, s, desc, n, max_len, cnt, nxt, (uint32_t*)lpt_order.p);
-        HIPTRY(hipGetLastError());
-      } else {
-        // (block shapes of 256 / 512 threads or 4 packets per thread measured the same or slower: 5.0-8.3 us,
-        // profiles/r06_lpt_shape_ab.jsonl)
-        hipLaunchKernelGGL((wgt::k_lpt_one<MODE>), dim3(lgrid), dim3(wgt::LPT_THREADS), 0, s, desc, n, max_len, cnt,
-                           nxt, (uint32_t*)lpt_order.p);
-        HIPTRY(hipGetLastError());
-      }
+      // (block shapes of 256 / 512 threads or 4 packets per thread measured the same or slower: 5.0-8.3 us,
+      // profiles/r06_lpt_shape_ab.jsonl)
+      hipLaunchKernelGGL((wgt::k_lpt_one<MODE>), dim3(lgrid), dim3(wgt::LPT_THREADS), 0, s, desc, n, max_len, cnt,
+                         nxt, (uint32_t*)lpt_order.p);
+      HIPTRY(hipGetLastError());
       lpt_hist.last_cnt = cnt;
       lpt_hist.par ^= 1u;
     } else if (!reuse_order) {
@@ -542,15 +490,14 @@ int plan_transport(wg_ctx* c, const wg_pkt* desc, uint32_t n, const uint8_t* in,
       hipLaunchKernelGGL((wgt::k_lpt_hist<MODE>), dim3(lgrid), dim3(wgt::LPT_THREADS), 0, s, desc, n, max_len, bh);
       hipLaunchKernelGGL((wgt::k_lpt_scatter<MODE>), dim3(lgrid), dim3(wgt::LPT_THREADS), 0, s, desc, n, max_len,
                          (const uint32_t*)bh, (uint32_t*)lpt_order.p, split,
-                         mixed ? (uint32_t*)c->lpt_nlong.p : nullptr, claim, P.claim_nc, P.claim_base);
+                         mixed ? (uint32_t*)c->lpt_nlong.p : nullptr);
       HIPTRY(hipGetLastError());
     }
     P.order = (const uint32_t*)lpt_order.p;
-    if (one) {
-      P.bin_cnt = lpt_hist.last_cnt;
+    if (one) {  // (a sparse order is a mixed launch's: n_long marks it as one)
+      P.bin_cnt = P.n_long = lpt_hist.last_cnt;
       P.bin_cap = n;
       P.split = split;
-      if (mixed) P.n_long = lpt_hist.last_cnt;  // (marks the launch as mixed; a wide plan's k_step is not)
     } else if (mixed) {
       P.n_long = (const uint32_t*)c->lpt_nlong.p;
     }
@@ -749,9 +696,9 @@ int launch_after_seal(wg_ctx* c, const wg_batch* sb, const wg_batch* ob, hipStre
   // the short-packet split plan in one launch (plan_transport's `one`) on the stream's own workspace
   wg_ctx::StreamWS* pws = nullptr;
   if (fused && c->stream_ws_on && !(sb->flags & WG_F_UNIFORM) && sb->max_len <= 2048u && c->lpt_one &&
-      !(c->lpt_fused && !c->stitch) && slot_plan(c, sb->flags, sb->n, sb->max_len).split > 0) {
+      slot_plan(c, sb->flags, sb->n, sb->max_len).split > 0) {
     pws = stream_ws(c, s);
-    if (pws && pws->used && (c->wsev & 2u)) HIPTRY(hipStreamWaitEvent(s, pws->ev, 0));
+    if (pws && pws->used) HIPTRY(hipStreamWaitEvent(s, pws->ev, 0));
     // the shared workspace sized too: a later call on a stream being captured into a graph (no workspace of
     // its own, and no allocation possible) plans there
     if (pws && (c->lpt_hist.ensure(2 * wgt::kPlanSet * sizeof(uint32_t)) != WG_OK ||
@@ -769,47 +716,17 @@ int launch_after_seal(wg_ctx* c, const wg_batch* sb, const wg_batch* ob, hipStre
     wgt::TransportParams PS{}, PO{};
     uint32_t gs = 0, go = 0;
     bool os = false, oo = false;
-    // dynamic claims (WG_CLAIM): mixed lengths on the persistent 8-lane plan with at least two packets
-    // per slot (the same test plan_transport makes for its longest-first pairs); up to 64 sub-orders,
-    // plan_transport picks how many divide its grid
-    uint32_t claim_nc = 0;
-    if (c->plan_err && __atomic_load_n(c->plan_err, __ATOMIC_ACQUIRE))
-      return fail(WG_EDEVICE, "a k_step_mixed_fused workgroup timed out waiting for its plan");
-    // the short-packet plan folded into the step launch (k_step_mixed_fused): a pinned error word first
-    bool defer = c->lpt_fused && !c->stitch;
-    if (defer && !c->plan_err) {
-      void* p = nullptr;
-      if (hipHostMalloc(&p, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess || !p) defer = false;
-      else {
-        memset(p, 0, 64);
-        c->plan_err = (uint32_t*)p;
-      }
-    }
-    if (c->claim && !(sb->flags & WG_F_UNIFORM) && sp.split == 0 && G == 8 && 2ull * sb->n > 8ull * cap &&
-        c->lpt_claim.ensure(64u * 64u) == WG_OK && c->lpt_chain.ensure(sizeof(uint2) * (size_t)sb->n) == WG_OK)
-      claim_nc = 64;
     rc = plan_transport<WG_MODE_SEAL>(c, sb->desc, sb->n, sb->in, sb->in_size, sb->out, sb->out_size, nullptr,
                                       sb->max_len, sb->flags, s, cap, G, plan_hist, plan_order, &PS, &gs, &os,
-                                      nullptr, true, false, sp.split, claim_nc ? (uint32_t*)c->lpt_claim.p : nullptr,
-                                      claim_nc, &defer, true);
+                                      nullptr, true, false, sp.split);
     if (rc == WG_OK)
       rc = plan_transport<WG_MODE_OPEN>(c, ob->desc, ob->n, ob->in, ob->in_size, ob->out, ob->out_size, ob->status,
                                         ob->max_len, ob->flags & ~WG_F_AFTER_SEAL, s, cap, G, plan_hist,
-                                        plan_order, &PO, &go, &oo, nullptr, true, true, sp.split, nullptr, 0,
-                                        nullptr, true);
+                                        plan_order, &PO, &go, &oo, nullptr, true, true, sp.split);
     // one issue-priority schedule over the seal and open halves (the rounds of both)
     if (PS.prio_step) PS.prio_step = PO.prio_step = 2u * PS.prio_step;
-    if (claim_nc) {
-      PS.chain_out = (uint2*)c->lpt_chain.p;
-      PO.claim_nc = PS.claim_nc;  // the open half replays the seal's log from the same first positions
-      PO.chain_in = (const uint2*)c->lpt_chain.p;
-    }
     if (rc == WG_OK && (gs != go || PS.slots != PO.slots || PS.order != PO.order || PS.bin_cnt != PO.bin_cnt))
       rc = fail(WG_EINVAL, "k_step: seal and open plans differ (%u / %u workgroups)", gs, go);
-    // a sparse (one-launch) order is read only by k_step_mixed* and k_step<8, 4, ..., kWideBins>
-    if (rc == WG_OK && PS.bin_cnt && !PS.n_long && !defer &&
-        !(G == 8 && c->step_wpe4 && 2ull * gs * wgt::TW <= cap && !c->stitch && !c->test_flip && !claim_nc))
-      rc = fail(WG_EINVAL, "k_step: a sparse plan without the kernel that reads it");
 #ifdef WG_DIAG
     if (PO.stamps) PO.stamps += 10ull * gs * wgt::TW;  // the open half's stamps after the seal half's
 #endif
@@ -820,53 +737,31 @@ int launch_after_seal(wg_ctx* c, const wg_batch* sb, const wg_batch* ob, hipStre
       // stop event): a separate hipEventRecord after the launch costs a 3-us gap between steps (IMIX 6%,
       // profiles/r06_ws_event_ab.jsonl). Not while the stream is being captured into a graph.
       hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      if (c->ws_ext && hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone && !ev)
+      if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone && !ev)
         stop_ev = pws ? pws->ev : (ordered ? c->ev_ws : nullptr);
 #define WG_XLAUNCH(kern, grid, block, shm, strm, ...) \
   hipExtLaunchKernelGGL(kern, grid, block, shm, strm, nullptr, stop_ev, 0u, __VA_ARGS__)
-      if (defer) {  // the planner's blocks first (as k_lpt_one's grid, with 64 x TW threads each), then the step's
-        uint32_t np = std::max<uint32_t>(1u, std::min<uint32_t>(wgt::LPT_MAX_BLOCKS, (sb->n + 1023u) / 1024u));
-        if (c->fused_np) np = std::min<uint32_t>(c->fused_np, std::max<uint32_t>(1u, sb->n / 256u));
-        uint32_t* cnt = const_cast<uint32_t*>(PS.bin_cnt);
-        uint32_t* nxt = (uint32_t*)c->lpt_hist.p + wgt::kPlanSet * c->lpt_hist.par;  // plan_transport flipped par
-        uint32_t* err = nullptr;
-        HIPTRY(hipHostGetDevicePointer((void**)&err, c->plan_err, 0));
-        if (sp.gs == 4)
-          WG_XLAUNCH(wgt::k_step_mixed_fused<4>, dim3(np + gs), dim3(64 * wgt::TW), 0, s, PS, PO, np, cnt, nxt, err,
-                             c->fused_poll);
-        else
-          WG_XLAUNCH(wgt::k_step_mixed_fused<8>, dim3(np + gs), dim3(64 * wgt::TW), 0, s, PS, PO, np, cnt, nxt, err,
-                             c->fused_poll);
-      } else if (claim_nc) WG_XLAUNCH((wgt::k_step_claim<8, 4>), dim3(gs), dim3(64 * wgt::TW), 0, s, PS, PO);
-      else if (PS.n_long && sp.gs == 4 && c->stitch)
-        WG_XLAUNCH((wgt::k_step_mixed<4, true>), dim3(gs), dim3(64 * wgt::TW), 0, s, PS, PO);
-      else if (PS.n_long && sp.gs == 4 && PS.bin_cnt && c->slot2 && c->slot2 < sp.split && c->key_slots < (1u << 24)) {
-        PS.split2 = PO.split2 = c->slot2;  // a third part: the grid's upper bound grows by one workgroup
-        WG_XLAUNCH((wgt::k_step_mixed<4, false, 2>), dim3(gs + 1), dim3(64 * wgt::TW), 0, s, PS, PO);
-      } else if (PS.n_long && sp.gs == 4) WG_XLAUNCH(wgt::k_step_mixed<4>, dim3(gs), dim3(64 * wgt::TW), 0, s, PS, PO);
-      else if (PS.n_long && c->stitch)
-        WG_XLAUNCH((wgt::k_step_mixed<8, true>), dim3(gs), dim3(64 * wgt::TW), 0, s, PS, PO);
-      else if (PS.n_long) WG_XLAUNCH(wgt::k_step_mixed<8>, dim3(gs), dim3(64 * wgt::TW), 0, s, PS, PO);
+      // mixed: one packet per slot, the long ones in 16-lane slots; tiny: a third part in 2-lane slots (needs the
+      // sparse order's counts; the grid's upper bound grows by one workgroup); pairs: a grid of at most half the
+      // resident waves (C2's 8-lane longest-first pairs) takes the build allocated for 4 waves per SIMD: no SGPR
+      // spills, C2 +0.7% in 3 alternations (profiles/r04_wpe_ab.txt)
+      const dim3 blk(64 * wgt::TW);
+      const bool mixed = PS.n_long != nullptr;
+      const bool tiny = mixed && sp.gs == 4 && PS.bin_cnt && c->slot2 && c->slot2 < sp.split && c->key_slots < (1u << 24);
+      const bool pairs = 2ull * gs * wgt::TW <= cap;
+      if (tiny) {
+        PS.split2 = PO.split2 = c->slot2;
+        WG_XLAUNCH((wgt::k_step_mixed<4, 2>), dim3(gs + 1), blk, 0, s, PS, PO);
+      } else if (mixed && sp.gs == 4) WG_XLAUNCH(wgt::k_step_mixed<4>, dim3(gs), blk, 0, s, PS, PO);
+      else if (mixed) WG_XLAUNCH(wgt::k_step_mixed<8>, dim3(gs), blk, 0, s, PS, PO);
 #ifdef WG_TEST_HOOKS
       else if (c->test_flip && G == 8)  // test hook build: the same body with the tag flip between the halves
-        WG_XLAUNCH((wgt::k_step<8, 4, true>), dim3(gs), dim3(64 * wgt::TW), 0, s, PS, PO, c->test_flip);
+        WG_XLAUNCH((wgt::k_step<8, 4, true>), dim3(gs), blk, 0, s, PS, PO, c->test_flip);
 #endif
-      else if (G == 16 && c->stitch)
-        WG_XLAUNCH((wgt::k_step<16, WG_STITCH_WPE, false, true>), dim3(gs), dim3(64 * wgt::TW), 0, s, PS, PO, 0u);
-      else if (G == 16) WG_XLAUNCH(wgt::k_step<16>, dim3(gs), dim3(64 * wgt::TW), 0, s, PS, PO, 0u);
-      else if (G == 4 && c->stitch)
-        WG_XLAUNCH((wgt::k_step<4, WG_STITCH_WPE, false, true>), dim3(gs), dim3(64 * wgt::TW), 0, s, PS, PO, 0u);
-      else if (G == 4) WG_XLAUNCH(wgt::k_step<4>, dim3(gs), dim3(64 * wgt::TW), 0, s, PS, PO, 0u);
-      else if (c->step_wpe4 && 2ull * gs * wgt::TW <= cap && c->stitch)
-        WG_XLAUNCH((wgt::k_step<8, WG_STITCH_WPE, false, true>), dim3(gs), dim3(64 * wgt::TW), 0, s, PS, PO, 0u);
-      else if (c->step_wpe4 && 2ull * gs * wgt::TW <= cap && PS.bin_cnt)  // the wide one-launch plan (sparse order)
-        WG_XLAUNCH((wgt::k_step<8, 4, false, false, (int)wgt::kWideBins>), dim3(gs), dim3(64 * wgt::TW), 0, s,
-                           PS, PO, 0u);
-      else if (c->step_wpe4 && 2ull * gs * wgt::TW <= cap)
-        WG_XLAUNCH((wgt::k_step<8, 4>), dim3(gs), dim3(64 * wgt::TW), 0, s, PS, PO, 0u);
-      else if (c->stitch)
-        WG_XLAUNCH((wgt::k_step<8, WG_STITCH_WPE, false, true>), dim3(gs), dim3(64 * wgt::TW), 0, s, PS, PO, 0u);
-      else WG_XLAUNCH(wgt::k_step<8>, dim3(gs), dim3(64 * wgt::TW), 0, s, PS, PO, 0u);
+      else if (G == 16) WG_XLAUNCH(wgt::k_step<16>, dim3(gs), blk, 0, s, PS, PO, 0u);
+      else if (G == 4) WG_XLAUNCH(wgt::k_step<4>, dim3(gs), blk, 0, s, PS, PO, 0u);
+      else if (pairs) WG_XLAUNCH((wgt::k_step<8, 4>), dim3(gs), blk, 0, s, PS, PO, 0u);
+      else WG_XLAUNCH(wgt::k_step<8>, dim3(gs), blk, 0, s, PS, PO, 0u);
 #undef WG_XLAUNCH
       const hipError_t e = hipGetLastError();
       record_end(c, s, ev);
@@ -883,7 +778,7 @@ int launch_after_seal(wg_ctx* c, const wg_batch* sb, const wg_batch* ob, hipStre
   if (pws) {  // the workspace's last use, for the next call that takes it
     if (stop_ev && rc == WG_OK) {
       pws->used = true;
-    } else if (c->wsev & 1u) {
+    } else {
       if (hipEventRecord(pws->ev, s) != hipSuccess) return fail(WG_EDEVICE, "hipEventRecord failed");
       pws->used = true;
     }
@@ -991,23 +886,12 @@ int wg_ctx_create(int device, uint32_t key_slots, wg_ctx** out) {
   // 16-lane slots, 0 never), WG_PRIO=0|1 (issue-priority schedule off / on for every batch).
   if (const char* e = getenv("WG_SLOT16")) c->slot16 = atoi(e);
   if (const char* e = getenv("WG_SLOT4")) c->slot4 = atoi(e);
-  if (const char* e = getenv("WG_SLOT4_PAIRS")) c->slot4_pairs = atoi(e) != 0;
-  if (const char* e = getenv("WG_SLOT4_SNAKE")) c->slot4_snake = atoi(e) != 0;
   if (const char* e = getenv("WG_MIXED_SPLIT")) c->mixed_split = (uint32_t)std::max(0, atoi(e));
   if (const char* e = getenv("WG_UNIFORM16")) c->uniform16 = (uint32_t)std::max(0, atoi(e));
   if (const char* e = getenv("WG_PRIO")) c->prio_mode = atoi(e);
-  if (const char* e = getenv("WG_STEP_WPE4")) c->step_wpe4 = atoi(e) != 0;
-  if (const char* e = getenv("WG_CLAIM")) c->claim = atoi(e) != 0;
-  if (const char* e = getenv("WG_STITCH")) c->stitch = atoi(e) != 0;
   if (const char* e = getenv("WG_LPT_ONE")) c->lpt_one = atoi(e) != 0;
-  if (const char* e = getenv("WG_LPT_WIDE")) c->lpt_wide = atoi(e) != 0;
-  if (const char* e = getenv("WG_LPT_FUSED")) c->lpt_fused = atoi(e) != 0;
   if (const char* e = getenv("WG_SLOT2")) c->slot2 = (uint32_t)std::max(0, atoi(e));
   if (const char* e = getenv("WG_STREAM_WS")) c->stream_ws_on = atoi(e) != 0;
-  if (const char* e = getenv("WG_WSEV")) c->wsev = (uint32_t)std::max(0, atoi(e));
-  if (const char* e = getenv("WG_WS_EXT")) c->ws_ext = atoi(e) != 0;
-  if (const char* e = getenv("WG_FUSED_POLL")) c->fused_poll = (uint32_t)std::max(0, atoi(e));
-  if (const char* e = getenv("WG_FUSED_NP")) c->fused_np = (uint32_t)std::max(0, atoi(e));
 #ifdef WG_TEST_HOOKS
   // fault-injection hooks exist only in the test library (make test: libwgaead_test.so); the product
   // library never reads these variables, so no environment can make it write wrong tags
@@ -1044,7 +928,6 @@ int wg_ctx_destroy(wg_ctx* c) {
                     &c->lpt_order, &c->lpt_hist2, &c->lpt_order2, &c->lpt_nlong, &c->h_desc, &c->h_in, &c->h_out, &c->h_aad, &c->h_status,
                     &c->h_keys})
     b->release();
-  if (c->plan_err) (void)hipHostFree(c->plan_err);
   for (auto& w : c->stream_ws) {
     w->hist.release();
     w->order.release();

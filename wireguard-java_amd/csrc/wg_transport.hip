@@ -49,7 +49,6 @@
 
 #include "wg_device.h"
 #include "wg_kernels.h"
-#include "wg_stitch.h"
 
 namespace wgt {
 
@@ -133,16 +132,15 @@ struct TransportParams {
   uint32_t pos_base;
   uint32_t split;
   uint32_t split2;  // k_step_mixed with GT = 2: keys <= split2 (> 0) take 2-lane slots, after the GS-lane part
-  // dynamic claims (k_step_claim, mixed-length batches): the longest-first order is dealt
-  // as claim_nc interleaved sub-orders (positions c, c + nc, c + 2 nc, ...), sub-order c to the workgroups
-  // b with b % nc == c; each slot starts on a static position and claims every later one from its
-  // sub-order's counter (claim[16 c], one 64-B line each, reset to claim_base by k_lpt_scatter), so a
-  // slot that finishes early takes the next-longest packet instead of a fixed one
-  uint32_t* claim;
-  uint32_t claim_nc;      // a power of two dividing the grid
-  uint32_t claim_base;    // slots per sub-order = the counters' initial value
-  uint2* chain_out;       // seal half of k_step_claim: per position {next position, next packet} of its slot
-  const uint2* chain_in;  // open half: the same chain, replayed (slot g opens exactly what it sealed)
+  // Five fields no code reads or writes (always zero). They were the dynamic-claim variant's (removed,
+  // docs/EXPERIMENTS.md) and keep the kernel arguments' layout: without them every kernel has the same
+  // registers, spills and occupancy, but k_step_mixed<4, 2> (IMIX) comes out of the register allocator and
+  // the scheduler as different code, and this layout's code is the one every measurement was taken on.
+  // Dropping them is a change to measure, not to make in passing.
+  uint32_t* unused_ptr0;
+  uint32_t unused_u0, unused_u1;
+  uint2* unused_ptr1;
+  const uint2* unused_ptr2;
   // 4-lane slots, one packet per slot (plan_transport): waves in one workgroup generation (workgroups
   // per CU x CUs x waves per workgroup); every odd generation takes its longest-first positions in
   // reverse, so the waves that share a SIMD get long and short packets in turn (0: no reversal)
@@ -322,9 +320,6 @@ __device__ __forceinline__ uint32_t batch_pos(uint32_t g, uint32_t k, uint32_t S
 // batch position -> packet index: the identity, the dense longest-first order, or the sparse one of k_lpt_one
 // (keys descending, key k's packets at order[k * bin_cap + i])
 constexpr uint32_t kFastBins = 6;  // keys 0..5: every packet of at most 2,048 B (33 blocks, 5 rounds of 8)
-// the same one-launch plan for other mixed batches whose keys fit 32 bins (max_len <= 15,808 B: C2's 9,000-B
-// packets are key 18), read by k_step<8, 4, ..., kWideBins>
-constexpr uint32_t kWideBins = 32;
 // k_lpt_one's per-key counters, kCntStride words apart (every planner workgroup adds to each once). 16 (a
 // 64-B line each) measured the same as 1: the planner's 5.1 us is not atomic contention
 // (profiles/r06_cnt_stride_ab.jsonl)
@@ -332,7 +327,7 @@ constexpr uint32_t kWideBins = 32;
 #define WG_CNT_STRIDE 1
 #endif
 constexpr uint32_t kCntStride = WG_CNT_STRIDE;
-template <int MX>  // MX: bins of the sparse order (kFastBins for the short-packet plan, kWideBins), 0: dense
+template <int MX>  // MX: bins of the sparse order (kFastBins, the short-packet plan), 0: dense
 __device__ __forceinline__ uint32_t pkt_at(const TransportParams& P, uint32_t pos) {
   if (MX && P.bin_cap) {
     // the counts through the scalar cache (constant for the launch), not held in SGPRs across the body
@@ -383,27 +378,18 @@ __device__ __forceinline__ uint32_t opaque_lane() {
 // 8 waves per SIMD).
 // iter: rounds this wave has run so far in the launch (the issue-priority schedule spans both
 // halves of a k_step launch).
-// Where a slot's packets come from (PM): kPosStatic, the snake over the grid (batch_pos); kPosClaim, a
-// static first position, then claims from the slot's sub-order counter, logged in P.chain_out when set;
-// kPosChain, the positions a kPosClaim seal half logged, in the same order.
-constexpr int kPosStatic = 0, kPosClaim = 1, kPosChain = 2;
-
-// ST (stitched Horner): a round's Horner steps run in the NEXT round of the packet, interleaved
-// into the first kStitchDR double rounds of its ChaCha20 block (wg_stitch.h); the next round's payload DMA is
-// issued after them, so the image still holds the round's MAC input while they read it. A packet's last
-// round takes its Horner steps after its XOR phase as before (nothing follows it to hide them in).
+// A slot's packets are the snake over the grid (batch_pos).
 // MX: the launch is a k_*_mixed part (its positions may map through k_lpt_one's sparse order)
-template <int MODE, int G = 8, bool VF = false, int PM = kPosStatic, bool ST = false, int MX = 0>
+template <int MODE, int G = 8, bool VF = false, int MX = 0>
 __device__ __forceinline__ void transport_body(const TransportParams& P, uint32_t blk, uint32_t wv, uint4* const img,
                                                SlotRec* const rec, uint32_t& iter) {
   static_assert(MODE == WG_MODE_SEAL || MODE == WG_MODE_OPEN, "transport modes only");
   static_assert(G == 2 || G == 4 || G == 8 || G == 16, "slots of 2, 4, 8 or 16 lanes");
-  static_assert(G != 2 || (MX && !VF && !ST), "2-lane slots: the short-packet split plan's tiny packets only");
+  static_assert(G != 2 || (MX && !VF), "2-lane slots: the short-packet split plan's tiny packets only");
 #ifdef WG_HORNER2
   static_assert(G != 2, "the two-chunk Horner assumes G >= 4");
 #endif
   static_assert(!VF || MODE == WG_MODE_OPEN, "verify-first is an open variant");
-  static_assert(!(ST && VF), "the verify-first open keeps the sequential Horner");
   constexpr uint32_t SH = G == 2 ? 1u : G == 4 ? 2u : G == 8 ? 3u : 4u;  // log2 G
   constexpr uint32_t JM = G - 1u;
   // a slot's record (SlotRec); 2-lane slots keep an 80-B one, so 32 of them per wave leave the launch at 6
@@ -426,18 +412,8 @@ __device__ __forceinline__ void transport_body(const TransportParams& P, uint32_
   // descriptor prefetch: the next packet's wg_pkt spread over the slot's lanes (desc_load)
   uint32_t gen = 0;
   uint32_t nxt;
-  // kPosClaim / kPosChain: the sub-order of this workgroup and the positions of the next / current packet
-  const uint32_t csub = PM != kPosStatic ? blk & (P.claim_nc - 1u) : 0u;
-  uint32_t npos = 0, cpos = 0;
   {
-    uint32_t pos;
-    if constexpr (PM == kPosStatic) {
-      pos = batch_pos(g, 0, S);
-    } else {  // slot index inside the sub-order's workgroups, then the sub-order's position of it
-      const uint32_t gl = (blk / P.claim_nc) * (TW * (64u / G)) + (g - blk * TW * (64u / G));
-      pos = csub + P.claim_nc * gl;
-    }
-    npos = pos;
+    const uint32_t pos = batch_pos(g, 0, S);
     nxt = pos < P.n ? pkt_at<MX>(P, pos) : ~0u;
   }
   uint4 dn = make_uint4(0u, 0u, 0u, 0u);  // this lane's part of the next descriptor (desc_word)
@@ -544,22 +520,9 @@ __device__ __forceinline__ void transport_body(const TransportParams& P, uint32_
       have = true;
       // prefetch the descriptor of the slot's following packet
       ++gen;
-      if constexpr (PM == kPosStatic) {
+      {
         const uint32_t pos = batch_pos(g, gen, S);
         nxt = pos < P.n ? pkt_at<MX>(P, pos) : ~0u;
-      } else if constexpr (PM == kPosClaim) {
-        cpos = npos;
-        uint32_t k = 0;
-        if (j == 0) k = atomicAdd(P.claim + 16u * csub, 1u);
-        const uint32_t pos = csub + P.claim_nc * bcastg<G, 0>(k);
-        nxt = pos < P.n ? (P.order ? P.order[pos] : pos) : ~0u;
-        npos = nxt != ~0u ? pos : ~0u;
-        if (P.chain_out && j == 0) P.chain_out[cpos] = make_uint2(npos, nxt);
-      } else {  // kPosChain
-        cpos = npos;
-        const uint2 cn = P.chain_in[cpos];  // every lane of the slot reads the same 8 B
-        npos = cn.x;
-        nxt = cn.y;
       }
       if constexpr (G == 2) {
         dn = desc_load2(P.desc, nxt, j);
@@ -579,15 +542,14 @@ __device__ __forceinline__ void transport_body(const TransportParams& P, uint32_
     const uint4 meta = RS(opaque_lane() >> SH).meta;
     const uint32_t len = meta.z;
     const uint32_t nb = (meta.w & 1u) ? ((len + 63u) >> 6) + 1u : 0u;
-    // ST: slots whose previous round (not their packet's last) still owes its Horner steps
-    const bool pend = ST && have && round > 0u && (meta.w & 1u);
-    const bool stitch = ST && __any(pend);
     uint32_t x[16];
     {
       // ---- payload prefetch: LDS-DMA straight into this lane's slice of the image ---------
-      // (no registers held across the ARX rounds; with stitched Horner steps pending, after them)
+      // (no registers held across the ARX rounds)
       const uint32_t lane = opaque_lane(), s = lane >> SH, j = lane & JM;
       const uint32_t b = G * round + j;
+      // (a lambda called once: written inline, the same statements allocate registers differently in every
+      // transport kernel, and this file's measurements are of the code as it is)
       auto payload_dma = [&]() {
       if (have && b < nb && b > 0u) {
         const uint32_t off = 64u * (b - 1u);
@@ -608,7 +570,7 @@ __device__ __forceinline__ void transport_body(const TransportParams& P, uint32_
         }
       }
       };
-      if (!stitch) payload_dma();
+      payload_dma();
       // ---- ChaCha20: block b = 8 round + j ----------------------------------------------
       if (G > 2 && __any(have && round == 0)) {  // a new packet: its columns 1..3 of the first round, once
         const uint32_t c = j & 3u;
@@ -632,47 +594,7 @@ __device__ __forceinline__ void transport_body(const TransportParams& P, uint32_
         const uint32_t H[12] = {bcastg<G, 1>(hc[0]), bcastg<G, 1>(hc[1]), bcastg<G, 1>(hc[2]), bcastg<G, 1>(hc[3]),
                                 bcastg<G, 2>(hc[0]), bcastg<G, 2>(hc[1]), bcastg<G, 2>(hc[2]), bcastg<G, 2>(hc[3]),
                                 bcastg<G, 3>(hc[0]), bcastg<G, 3>(hc[1]), bcastg<G, 3>(hc[2]), bcastg<G, 3>(hc[3])};
-        if constexpr (!ST) {
-          chacha20_block_hoisted(RS(s).key, b, meta.x, meta.y, 0u, H, x);
-        } else {
-          // the same block in two parts: the first kStitchDR double rounds (with the pending Horner steps of the
-          // previous round when any slot has them), then the payload DMA, then the rest and the feed-forward
-          const uint4* kl = RS(s).key;
-          uint4 ka = kl[0], kb = kl[1];
-          x[0] = 0x61707865u; x[1] = H[0]; x[2] = H[4]; x[3] = H[8];
-          x[4] = ka.x; x[5] = H[1]; x[6] = H[5]; x[7] = H[9];
-          x[8] = kb.x; x[9] = H[2]; x[10] = H[6]; x[11] = H[10];
-          x[12] = b; x[13] = H[3]; x[14] = H[7]; x[15] = H[11];
-          if (stitch) {
-            // the previous round kp's window: chunks [4 G kp - 4, 4 G kp + 4 G - 4) (round 0's first four are the
-            // zeroed key-block lane, so every lane takes exactly four steps); lane j's chunks c0 + G t sit in one
-            // image row (c0 & 3), G / 4 lanes apart. Lanes without a pending round compute on a clamped address
-            // and their accumulator is not used (a new packet resets it in its round 0 scan).
-            const uint32_t kp = round - 1u;
-            const uint32_t nc = (len + 15u) >> 4, M = nc + 1u, Dp = G * ((M + JM) >> SH) - M;
-            const uint32_t u = 4u * G * kp + ((j - ((4u * G * kp - 4u + Dp) & JM)) & JM);  // c0 + 4
-            const uint32_t lanepart = ((u >> 2) - G * kp) & (G / 4u - 1u);
-            const uint32_t addr = (uint32_t)(uintptr_t)&img[64u * (u & 3u) + (lane & ~JM) + lanepart];
-            const uint4 q0 = RS(s).R0, q1 = RS(s).R1, q2 = RS(s).R2;
-            const uint32_t R[5] = {q0.x, q0.y, q0.z, q0.w, q1.x};
-            const uint32_t Rs[4] = {q1.y, q1.z, q1.w, q2.x};
-            // a lane whose first chunk of round 0's window lies before the data (u < 4: chunks -4..-1) adds it
-            // without the 2^128 bit, so the zeroed chunk adds nothing to its still-zero accumulator
-            const uint32_t hib0 = (kp == 0u && u < 4u) ? 0u : (1u << 24);
-            chacha20_rounds_stitch_asm<G>(x, acc, R, Rs, addr, hib0);
-            payload_dma();
-          } else {
-            chacha20_rounds_head_asm(x);
-          }
-          chacha20_rounds_tail_asm(x);
-          asm volatile("" ::: "memory");
-          ka = kl[0];
-          kb = kl[1];
-          x[0] += 0x61707865u; x[1] += 0x3320646eu; x[2] += 0x79622d32u; x[3] += 0x6b206574u;
-          x[4] += ka.x; x[5] += ka.y; x[6] += ka.z; x[7] += ka.w;
-          x[8] += kb.x; x[9] += kb.y; x[10] += kb.z; x[11] += kb.w;
-          x[12] += b; x[13] += meta.x; x[14] += meta.y;
-        }
+        chacha20_block_hoisted(RS(s).key, b, meta.x, meta.y, 0u, H, x);
       }
     }
 
@@ -723,11 +645,6 @@ __device__ __forceinline__ void transport_body(const TransportParams& P, uint32_
               store_chunk(dst + 16u * q, cb, o, oal);
           }
         }
-      }
-      // ST: the key-block lane's image slice is round 0's chunks -4..-1 of the stitched window: zero
-      if (ST && have && round == 0u && j == 0u) {
-#pragma unroll
-        for (uint32_t q = 0; q < 4u; ++q) img[64u * q + lane] = make_uint4(0u, 0u, 0u, 0u);
       }
     }
     // the length block le64(0) || le64(len) is MAC chunk nc (the first after the data): the lane
@@ -790,8 +707,8 @@ __device__ __forceinline__ void transport_body(const TransportParams& P, uint32_
     }
 
     WG_PH(3);
-    // ---- Poly1305 over this round's chunks (ST: only a packet's last round; the others run stitched) -------
-    if (have && (meta.w & 1u) && mac_pass && (!ST || G * (round + 1u) >= nb)) {
+    // ---- Poly1305 over this round's chunks ------------------------------------------------------
+    if (have && (meta.w & 1u) && mac_pass) {
       const uint32_t lane = opaque_lane(), s = lane >> SH, j = lane & JM;
       {
         const uint32_t nc = (len + 15u) >> 4;
@@ -1033,17 +950,14 @@ __global__ void __launch_bounds__(64 * TW) __attribute__((amdgpu_waves_per_eu(8)
   TransportParams Q;
   uint32_t qb = 0, iter = 0;
   const int g = mixed_part<GS>(P, blockIdx.x, Q, qb);
-  if (g == 16) transport_body<MODE, 16, VF, kPosStatic, false, (int)kFastBins>(Q, qb, wv, img_[wv], rec_[wv], iter);
-  else if (g == GS) transport_body<MODE, GS, VF, kPosStatic, false, (int)kFastBins>(Q, qb, wv, img_[wv], rec_[wv], iter);
+  if (g == 16) transport_body<MODE, 16, VF, (int)kFastBins>(Q, qb, wv, img_[wv], rec_[wv], iter);
+  else if (g == GS) transport_body<MODE, GS, VF, (int)kFastBins>(Q, qb, wv, img_[wv], rec_[wv], iter);
 }
 
-#ifndef WG_STITCH_WPE
-#define WG_STITCH_WPE 5  // waves per SIMD the stitched kernels' register allocation targets (96 VGPRs: no spill)
-#endif
 // GT = 2: a third part after the GS-lane one, the tiny packets (keys <= split2) in 2-lane slots (32 per wave:
 // a 40-B packet's two blocks fill its lanes instead of half of a 4-lane slot). Its records need twice the LDS.
-template <int GS = 8, bool ST = false, int GT = 0>
-__global__ void __launch_bounds__(64 * TW) __attribute__((amdgpu_waves_per_eu(ST ? WG_STITCH_WPE : 8)))
+template <int GS = 8, int GT = 0>
+__global__ void __launch_bounds__(64 * TW) __attribute__((amdgpu_waves_per_eu(8)))
 k_step_mixed(TransportParams S, TransportParams O) {
   __shared__ uint4 img_[TW][4 * 64];
   // slot records: 128 B per GS- or 16-lane slot, 80 B per 2-lane slot (transport_body's kRecStride)
@@ -1056,18 +970,18 @@ k_step_mixed(TransportParams S, TransportParams O) {
   const int g = mixed_part<GS, GT>(S, blockIdx.x, QS, qb);
   (void)mixed_part<GS, GT>(O, blockIdx.x, QO, qb2);  // the same split: the open batch has the seal's lengths
   if (g == 16) {
-    transport_body<WG_MODE_SEAL, 16, false, kPosStatic, ST, (int)kFastBins>(QS, qb, wv, img_[wv], rec, iter);
+    transport_body<WG_MODE_SEAL, 16, false, (int)kFastBins>(QS, qb, wv, img_[wv], rec, iter);
     asm volatile("s_waitcnt vmcnt(0)\n\tbuffer_inv sc0" ::: "memory");
-    transport_body<WG_MODE_OPEN, 16, false, kPosStatic, ST, (int)kFastBins>(QO, qb, wv, img_[wv], rec, iter);
+    transport_body<WG_MODE_OPEN, 16, false, (int)kFastBins>(QO, qb, wv, img_[wv], rec, iter);
   } else if (g == GS) {
-    transport_body<WG_MODE_SEAL, GS, false, kPosStatic, ST, (int)kFastBins>(QS, qb, wv, img_[wv], rec, iter);
+    transport_body<WG_MODE_SEAL, GS, false, (int)kFastBins>(QS, qb, wv, img_[wv], rec, iter);
     asm volatile("s_waitcnt vmcnt(0)\n\tbuffer_inv sc0" ::: "memory");
-    transport_body<WG_MODE_OPEN, GS, false, kPosStatic, ST, (int)kFastBins>(QO, qb, wv, img_[wv], rec, iter);
+    transport_body<WG_MODE_OPEN, GS, false, (int)kFastBins>(QO, qb, wv, img_[wv], rec, iter);
   } else if constexpr (GT != 0) {
     if (g == GT) {
-      transport_body<WG_MODE_SEAL, GT, false, kPosStatic, false, (int)kFastBins>(QS, qb, wv, img_[wv], rec, iter);
+      transport_body<WG_MODE_SEAL, GT, false, (int)kFastBins>(QS, qb, wv, img_[wv], rec, iter);
       asm volatile("s_waitcnt vmcnt(0)\n\tbuffer_inv sc0" ::: "memory");
-      transport_body<WG_MODE_OPEN, GT, false, kPosStatic, false, (int)kFastBins>(QO, qb, wv, img_[wv], rec, iter);
+      transport_body<WG_MODE_OPEN, GT, false, (int)kFastBins>(QO, qb, wv, img_[wv], rec, iter);
     }
   }
 }
@@ -1107,7 +1021,7 @@ k_duplex(TransportParams S, TransportParams O, uint32_t seal_blocks, uint32_t op
 // WPE: the waves per SIMD the register allocation targets. 8 (64 VGPRs) everywhere, except a grid
 // that holds at most half the resident waves anyway (the persistent longest-first pairs of a
 // mixed batch: 4 waves per SIMD), which takes the WPE = 4 build (66 VGPRs and no SGPR spills,
-// against 64 VGPRs and 12 SGPRs spilled to VGPR lanes; WG_STEP_WPE4=0 for the other).
+// against 64 VGPRs and 12 SGPRs spilled to VGPR lanes).
 // Test hook of k_step (WG_TEST_STEP_FLIP, never set in production): between the two halves, lane 0 of
 // each slot flips bit 0 of the tag its seal wrote for the slot's first packet (batch position g) when
 // that packet's index is a multiple of S.test_flip. The open half then rejects it and the ciphertext
@@ -1129,34 +1043,19 @@ __device__ __forceinline__ void step_test_flip(const TransportParams& S, uint32_
 
 // FLIP: the test-hook instantiation (WG_TEST_STEP_FLIP), launched only by the test library (WG_TEST_HOOKS);
 // the product instantiations carry no hook code at all.
-template <int G = 8, int WPE = 8, bool FLIP = false, bool ST = false, int MX = 0>
+template <int G = 8, int WPE = 8, bool FLIP = false, int MX = 0>
 __global__ void __launch_bounds__(64 * TW) __attribute__((amdgpu_waves_per_eu(WPE)))
 k_step(TransportParams S, TransportParams O, uint32_t test_flip) {
   __shared__ uint4 img_[TW][4 * 64];
   __shared__ SlotRec rec_[TW][64 / G < 8 ? 8 : 64 / G];
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   uint32_t iter = 0;  // one issue-priority schedule over both halves (plan_transport: prio_step of the step)
-  transport_body<WG_MODE_SEAL, G, false, kPosStatic, ST, MX>(S, blockIdx.x, wv, img_[wv], rec_[wv], iter);
+  transport_body<WG_MODE_SEAL, G, false, MX>(S, blockIdx.x, wv, img_[wv], rec_[wv], iter);
   // the open reads the ciphertext and tags this wave just stored: wait until the stores are
   // performed and drop this CU's L1 lines (an in-place seal read the plaintext through them)
   asm volatile("s_waitcnt vmcnt(0)\n\tbuffer_inv sc0" ::: "memory");
   if constexpr (FLIP) step_test_flip<G>(S, blockIdx.x, wv, test_flip);
-  transport_body<WG_MODE_OPEN, G, false, kPosStatic, ST, MX>(O, blockIdx.x, wv, img_[wv], rec_[wv], iter);
-}
-
-// k_step with dynamic claims (mixed-length batches, WG_CLAIM): the seal half claims its slots' packets
-// from the sub-order counters and logs them per position; the open half replays that log, so slot g
-// opens exactly what it sealed (the same wave wrote it: the half boundary below orders the accesses).
-template <int G = 8, int WPE = 4>
-__global__ void __launch_bounds__(64 * TW) __attribute__((amdgpu_waves_per_eu(WPE)))
-k_step_claim(TransportParams S, TransportParams O) {
-  __shared__ uint4 img_[TW][4 * 64];
-  __shared__ SlotRec rec_[TW][8];
-  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  uint32_t iter = 0;
-  transport_body<WG_MODE_SEAL, G, false, kPosClaim>(S, blockIdx.x, wv, img_[wv], rec_[wv], iter);
-  asm volatile("s_waitcnt vmcnt(0)\n\tbuffer_inv sc0" ::: "memory");
-  transport_body<WG_MODE_OPEN, G, false, kPosChain>(O, blockIdx.x, wv, img_[wv], rec_[wv], iter);
+  transport_body<WG_MODE_OPEN, G, false, MX>(O, blockIdx.x, wv, img_[wv], rec_[wv], iter);
 }
 
 // ---- longest-first order for mixed-length batches (LPT) ----------------------------------
@@ -1198,10 +1097,7 @@ __global__ void __launch_bounds__(LPT_THREADS) k_lpt_hist(const wg_pkt* d, uint3
 template <int MODE>
 __global__ void __launch_bounds__(LPT_THREADS) k_lpt_scatter(const wg_pkt* d, uint32_t n, uint32_t max_len,
                                                              const uint32_t* bh, uint32_t* order, uint32_t split,
-                                                             uint32_t* n_long, uint32_t* claim, uint32_t claim_nc,
-                                                             uint32_t claim_base) {
-  // the dynamic-claim counters of the launch this order is for (k_step_claim): one 64-B line each
-  if (claim && blockIdx.x == 0 && threadIdx.x < claim_nc) claim[16u * threadIdx.x] = claim_base;
+                                                             uint32_t* n_long) {
   __shared__ uint32_t all[LPT_MAX_BLOCKS * LPT_BINS];  // every block's histogram (coalesced load)
   __shared__ uint32_t tot[LPT_BINS], base[LPT_BINS];
   for (uint32_t e = threadIdx.x; e < gridDim.x * LPT_BINS; e += LPT_THREADS) all[e] = bh[e];
@@ -1260,27 +1156,30 @@ __global__ void __launch_bounds__(LPT_THREADS) k_lpt_scatter(const wg_pkt* d, ui
   for (uint32_t i = lo + threadIdx.x; i < hi; i += LPT_THREADS) order[atomicAdd(&base[lpt_key<MODE>(d, i, max_len)], 1u)] = i;
 }
 
-// k_lpt_one's counter set per call: the counts kCntStride words apart, the fused step's publication count at
-// kPlanDone), two sets used in turn
-constexpr uint32_t kPlanDone = kWideBins * kCntStride > 32u ? kWideBins * kCntStride : 32u;
-constexpr uint32_t kPlanSet = kPlanDone + 32u;  // words per set (the publication count on a line of its own)
+// k_lpt_one's counter set per call: kFastBins counts kCntStride words apart, each set on 64-B lines of its own
+// (the next set is zeroed while this one takes atomics); two sets used in turn
+constexpr uint32_t kPlanSet = (kFastBins * kCntStride + 15u) / 16u * 16u;  // words per set
 
-// The body of k_lpt_one for block `blk` of `nblk` with `threads` threads over NB keys: h / base are NB words of LDS.
+// One launch instead of k_lpt_hist + k_lpt_scatter, for batches whose keys fit kFastBins (max_len <= 2,048 B,
+// the short-packet plan): each block counts its range's keys in LDS, takes its base in every non-empty key
+// with ONE atomicAdd on that key's global counter, and ranks its packets into the key's region of a sparse
+// order (key k at order[k * n]). No grid-wide barrier: the consumer derives the positions from the counts.
+// The counters are double-buffered by call (cnt for this call, zero on entry; cnt_next zeroed here for the
+// next), so no memset launch either. Order inside a key: arbitrary (every position of the order is a packet).
 // A thread takes KPT packets per trip, their descriptor loads issued together, and when the block's range is
 // one trip (the usual case) keeps the keys for the scatter pass: two load latencies per plan, not 2 x trips.
-template <int MODE, int KPT = 1, uint32_t NB = kFastBins>
-__device__ __forceinline__ void lpt_one_body(const wg_pkt* d, uint32_t n, uint32_t max_len, uint32_t* cnt,
-                                             uint32_t* cnt_next, uint32_t* order, uint32_t blk, uint32_t nblk,
-                                             uint32_t threads, uint32_t* h, uint32_t* base) {
+// (THREADS, KPT: the block shape)
+template <int MODE, uint32_t THREADS = LPT_THREADS, int KPT = 1>
+__global__ void __launch_bounds__(THREADS) k_lpt_one(const wg_pkt* d, uint32_t n, uint32_t max_len, uint32_t* cnt,
+                                                     uint32_t* cnt_next, uint32_t* order) {
+  constexpr uint32_t NB = kFastBins;
+  __shared__ uint32_t h[NB], base[NB];
   if (threadIdx.x < NB) h[threadIdx.x] = 0;
-  // the next call's counts ([0, NB)) and k_step_mixed_fused's publication count (kPlanDone: its own line,
-  // away from the counts' atomics)
-  if (blk == 0 && ((threadIdx.x < kWideBins * kCntStride && threadIdx.x % kCntStride == 0u) || threadIdx.x == kPlanDone))
-    cnt_next[threadIdx.x] = 0;
+  if (blockIdx.x == 0 && threadIdx.x < NB) cnt_next[threadIdx.x * kCntStride] = 0;  // the next call's counts
   __syncthreads();
-  const uint32_t per = (n + nblk - 1u) / nblk;
-  const uint32_t lo = min(n, blk * per), hi = min(n, lo + per);
-  const uint32_t lane = threadIdx.x & 63u, span = threads * KPT;
+  const uint32_t per = (n + gridDim.x - 1u) / gridDim.x;
+  const uint32_t lo = min(n, blockIdx.x * per), hi = min(n, lo + per);
+  const uint32_t lane = threadIdx.x & 63u, span = THREADS * KPT;
   // LDS atomics are aggregated per wave and key: one ballot per key, then ONE ds_add_rtn in which lane k adds
   // key k's lane count to slots[k] (six independent adds, not a chain of six round trips), one bpermute for
   // each lane's base in its key and mbcnt for its rank among the wave's lanes of that key
@@ -1301,7 +1200,7 @@ __device__ __forceinline__ void lpt_one_body(const wg_pkt* d, uint32_t n, uint32
   auto keys_at = [&](uint32_t i0, uint32_t (&key)[KPT]) {  // every lane of a wave takes part in each trip
 #pragma unroll
     for (int t = 0; t < KPT; ++t) {
-      const uint32_t i = i0 + t * threads + threadIdx.x;
+      const uint32_t i = i0 + t * THREADS + threadIdx.x;
       key[t] = i < hi ? lpt_key<MODE>(d, i, max_len) : NB;
     }
   };
@@ -1322,113 +1221,11 @@ __device__ __forceinline__ void lpt_one_body(const wg_pkt* d, uint32_t n, uint32
     if (!one_trip) keys_at(i0, key);
 #pragma unroll
     for (int t = 0; t < KPT; ++t) {
-      const uint32_t i = i0 + t * threads + threadIdx.x;
+      const uint32_t i = i0 + t * THREADS + threadIdx.x;
       const uint32_t at = wave_rank(base, key[t]);
       if (i < hi) order[at] = i;
     }
   }
-}
-
-// One launch instead of k_lpt_hist + k_lpt_scatter, for batches whose keys fit kFastBins (max_len <= 2,048 B,
-// the short-packet plan): each block counts its range's keys in LDS, takes its base in every non-empty key
-// with ONE atomicAdd on that key's global counter, and ranks its packets into the key's region of a sparse
-// order (key k at order[k * n]). No grid-wide barrier: the consumer derives the positions from the counts.
-// The counters are double-buffered by call (cnt for this call, zero on entry; cnt_next zeroed here for the
-// next), so no memset launch either. Order inside a key: arbitrary (every position of the order is a packet).
-// (THREADS, KPT: the block shape)
-template <int MODE, uint32_t THREADS = LPT_THREADS, int KPT = 1, uint32_t NB = kFastBins>
-__global__ void __launch_bounds__(THREADS) k_lpt_one(const wg_pkt* d, uint32_t n, uint32_t max_len, uint32_t* cnt,
-                                                     uint32_t* cnt_next, uint32_t* order) {
-  __shared__ uint32_t h[NB], base[NB];
-  lpt_one_body<MODE, KPT, NB>(d, n, max_len, cnt, cnt_next, order, blockIdx.x, gridDim.x, THREADS, h, base);
-}
-
-// k_step_mixed with its planning folded in (WG_LPT_FUSED, the short-packet plan): workgroups [0, np) plan as
-// k_lpt_one does and then publish (their stores acknowledged, one release count per workgroup in cnt[kPlanDone]); the
-// other workgroups wait for all np publications (one acquire poll per workgroup, s_sleep between polls) and
-// then run k_step_mixed's body. The planners are the lowest workgroup indices, so they are dispatched before
-// any waiting workgroup can occupy the machine. A wait is bounded (kPlanWaitTicks of s_memrealtime); a
-// workgroup that runs out of it writes *err and does no work, and the host fails the next call.
-constexpr uint64_t kPlanWaitTicks = 5000000;  // 50 ms at 100 MHz
-#ifdef WG_DIAG  // diagnostic build: s_memrealtime per workgroup (tools/fused_timing.py): a planner's start and
-                // publication, a consumer's arrival, release from the wait and end
-constexpr size_t kFusedStampOff = 400000;
-#define WG_FUSED_STAMP(j, v) \
-  if (S.stamps && threadIdx.x == 0) S.stamps[kFusedStampOff + 3u * blockIdx.x + (j)] = (v)
-#else
-#define WG_FUSED_STAMP(j, v)
-#endif
-template <int GS = 8, bool ST = false>
-__global__ void __launch_bounds__(64 * TW) __attribute__((amdgpu_waves_per_eu(ST ? WG_STITCH_WPE : 8)))
-k_step_mixed_fused(TransportParams S, TransportParams O, uint32_t np, uint32_t* cnt, uint32_t* cnt_next, uint32_t* err,
-                   uint32_t poll) {
-  __shared__ uint4 img_[TW][4 * 64];
-  __shared__ SlotRec rec_[TW][64 / GS];
-  WG_FUSED_STAMP(0, __builtin_amdgcn_s_memrealtime());
-  if (blockIdx.x < np) {
-    uint32_t* h = (uint32_t*)&img_[0][0];
-    lpt_one_body<WG_MODE_SEAL, 4>(S.desc, S.n, S.max_len, cnt, cnt_next, (uint32_t*)S.order, blockIdx.x, np, 64u * TW,
-                               h, h + 8);
-    // every wave's order stores acknowledged by its L2, then one release (one L2 write-back) per workgroup
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(&cnt[kPlanDone], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    WG_FUSED_STAMP(1, __builtin_amdgcn_s_memrealtime());
-    return;
-  }
-  __shared__ uint32_t go;
-  if (threadIdx.x == 0) {
-    uint32_t ok = 1u;
-    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-    // relaxed polls (an acquire per poll would invalidate the L2 every time), one acquire fence after
-    // poll (WG_FUSED_POLL, A/B): 0 agent-scope loads, 1 system-scope loads, 2 read-modify-writes (performed at
-    // the coherence point), at a quarter of the rate
-    auto published = [&]() {
-      if (poll == 1) return __hip_atomic_load(&cnt[kPlanDone], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      if (poll == 2) return __hip_atomic_fetch_add(&cnt[kPlanDone], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return __hip_atomic_load(&cnt[kPlanDone], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
-    while (published() < np) {
-      if (__builtin_amdgcn_s_memrealtime() - t0 > kPlanWaitTicks) {
-        __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        ok = 0u;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(8);  // ~0.2 us: the polls of every waiting workgroup meet at one line
-      if (poll == 2) {
-        __builtin_amdgcn_s_sleep(8);
-        __builtin_amdgcn_s_sleep(8);
-        __builtin_amdgcn_s_sleep(8);
-      }
-    }
-    // no agent-scope acquire here: its L2 invalidation, made by every waiting workgroup at about the same time,
-    // cost the step 28 us (IMIX, profiles/r06_fused_ab.jsonl). None is needed on this hardware path: the plan's
-    // lines cannot be in this XCD's L2 (a dispatch starts with the L2s invalidated, and no workgroup of this
-    // launch reads them before the plan is published: the planners only write them, by stores and by atomics
-    // performed at the device's coherence point), and the planners' release wrote them back; only this CU's
-    // L1 is invalidated, as between a step's halves
-    asm volatile("s_waitcnt vmcnt(0)\n\tbuffer_inv sc0" ::: "memory");
-    go = ok;
-    WG_FUSED_STAMP(1, __builtin_amdgcn_s_memrealtime());
-  }
-  __syncthreads();
-  if (!go) return;
-  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  TransportParams QS, QO;
-  uint32_t qb = 0, qb2 = 0, iter = 0;
-  const uint32_t blk = blockIdx.x - np;
-  const int g = mixed_part<GS>(S, blk, QS, qb);
-  (void)mixed_part<GS>(O, blk, QO, qb2);
-  if (g == 16) {
-    transport_body<WG_MODE_SEAL, 16, false, kPosStatic, ST, (int)kFastBins>(QS, qb, wv, img_[wv], rec_[wv], iter);
-    asm volatile("s_waitcnt vmcnt(0)\n\tbuffer_inv sc0" ::: "memory");
-    transport_body<WG_MODE_OPEN, 16, false, kPosStatic, ST, (int)kFastBins>(QO, qb, wv, img_[wv], rec_[wv], iter);
-  } else if (g == GS) {
-    transport_body<WG_MODE_SEAL, GS, false, kPosStatic, ST, (int)kFastBins>(QS, qb, wv, img_[wv], rec_[wv], iter);
-    asm volatile("s_waitcnt vmcnt(0)\n\tbuffer_inv sc0" ::: "memory");
-    transport_body<WG_MODE_OPEN, GS, false, kPosStatic, ST, (int)kFastBins>(QO, qb, wv, img_[wv], rec_[wv], iter);
-  }
-  WG_FUSED_STAMP(2, __builtin_amdgcn_s_memrealtime());
 }
 
 // ---- wire framing (TransportPacket.java:18-35) --------------------------------------------
