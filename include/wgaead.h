@@ -432,6 +432,121 @@ int wg_tx_counters_get(wg_ctx* ctx, uint32_t first_slot, uint32_t n, uint64_t* c
 int wg_tx_reserve(wg_ctx* ctx, uint32_t max_packets);
 int wg_tx_plan(wg_ctx* ctx, const wg_tx_batch* batch, void* stream);
 
+/* ---- receive side before and after open: sessions by index, tun delivery list ----
+ * The device counterpart of the reference's inbound path around decipher, for a whole UDP ring, so that
+ * a UDP ring becomes a plaintext ring and an ordered list of tun writes without per-packet host work:
+ *  - the type byte that picks the packet class (PacketElement.java:107-113: 1 initiation, 2 response,
+ *    4 transport, anything else throws);
+ *  - the session of a transport packet's receiver index (PeerList.java:53-67 drops an unknown index at
+ *    :61-65; TransportManager.java:70-77 drops a peer without a session at :73-77);
+ *  - the open descriptor (UndecryptedIncomingTransport.java:20-33), as wg_parse_open builds it;
+ *  - after the open, which packets go to the tun device and in which order
+ *    (TransportManager.processDecryptedTransport, TransportManager.java:98-119, queues them one by one).
+ *
+ * wg_rx_sessions_set(ctx, indices, key_slots, n): replaces the whole receiver index -> key slot table
+ *   (PeerList's index -> peer array, PeerList.java:53-67,:157-173, plus the peer's session,
+ *   TransportManager.java:70-77); n = 0 clears it. Indices are arbitrary 32-bit values (the reference's
+ *   small array indices and WireGuard's random ones, 0 and 0xFFFFFFFF included). A repeated index is
+ *   WG_EINVAL, a key slot >= the key table WG_ERANGE; nothing changes on error. Synchronous, like
+ *   wg_routes_set, and ordered after every receive plan queued before it. On the device the table is an
+ *   open-addressing hash table built on the host: capacity = the smallest power of two >= max(16, 4 n),
+ *   8-byte entries {index, key_slot + 1} (0: empty), bucket = fmix32(index) & (capacity - 1) with
+ *   MurmurHash3's 32-bit finaliser, linear probing. Its header (entries, mask, count) keeps one device address for
+ *   the life of the context, so a captured plan needs no re-capture after a table change. There is no
+ *   single-entry insert or remove: rekeying one peer sends the table again.
+ *
+ * wg_rx_plan(ctx, b, stream): wire packet i is wire[o .. o + wl), o = pkt_off[i], wl = pkt_len[i]. The
+ *   checks, in this order:
+ *   1. wl == 0, o > wire_size or wl > wire_size - o: WG_PKT_BADHDR.
+ *   2. t = wire[o]: 1 or 2 (InitiationPacket.TYPE, ResponsePacket.TYPE): WG_PKT_HANDSHAKE whatever its
+ *      length (the host validates and handles it); any other t != 4: WG_PKT_BADHDR (PacketElement.java:112).
+ *   3. t == 4 and wl < 32: WG_PKT_BADHDR; otherwise len = wl - 32 (only the type byte of the header is
+ *      checked, UndecryptedIncomingTransport.java:24-26).
+ *   4. the receiver index (LE32 at o + 4) is not in the session table: WG_PKT_NOSESSION.
+ *   5. len > max_len: WG_PKT_TOOLONG.
+ *   6. placement. WG_RX_PT_AFTER (the reference's layout, UndecryptedIncomingTransport.java:30): out_off
+ *      = o + wl in the wire buffer; a plaintext that overruns wire_size is WG_PKT_BADHDR, as in
+ *      wg_parse_open; pt_used = 0. WG_RX_PT_PACKED: out_off = pt_base + C_i, C_i = the sum of
+ *      align16(len_j) over all j < i that passed steps 1-5; a packet with out_off + len > pt_size is
+ *      WG_PKT_TOOLONG but still counts in C; pt_used = the final C. Every out_off is 16-byte aligned
+ *      when pt_base is, and the plaintexts to copy back are the first min(pt_used, pt_size - pt_base)
+ *      bytes at pt_base.
+ *   A packet that passes has rx_status WG_PKT_OK and desc = {in_off = o + 16, out_off, counter = LE64
+ *   at o + 8, len, key_slot}. Every other packet has len = WG_LEN_INVALID (wg_open_batch skips it with
+ *   WG_PKT_BADTAG), counter = 0, in_off = o + 16 (modulo 2^64), out_off = o + wl (AFTER, modulo 2^64) or
+ *   pt_base (PACKED), and key_slot = the session's slot if step 4 succeeded, else 0. All n descriptors
+ *   and statuses are written. host_list[0 .. n_host) holds the batch indices of the WG_PKT_HANDSHAKE
+ *   packets in ascending order; n_open counts the WG_PKT_OK ones. n = 0 writes only the summary (zeros).
+ *   desc_out: 16-byte aligned; summary: 8-byte aligned. Asynchronous on `stream`; run wg_open_batch
+ *   on desc_out on the same stream, with a status array of its own (wg_rx_deliver merges the two).
+ *
+ * wg_rx_deliver(ctx, b, stream): after wg_open_batch and wg_rx_check on the same stream. final_status[i]
+ *   = plan_status[i] if that is not WG_PKT_OK, else open_status[i] (final_status may alias neither).
+ *   items[0 .. n_items) is the stable compaction, in batch order, of the packets whose final status is
+ *   WG_PKT_OK: {off = desc[i].out_off, len, key_slot}; index_out (may be NULL) holds their batch indices.
+ *   delivered = {bytes = the sum of len over the items, n_items, n_keepalive = packets whose final
+ *   status is WG_PKT_KEEPALIVE}. The host writes n_items packets to the tun device in arrival order and
+ *   never looks at a status. items: 16-byte aligned; delivered: 8-byte aligned.
+ *
+ * Both calls rank over the whole batch without any wait between workgroups (a pass of per-workgroup
+ * sums, one small scan, a pass that places); their scratch is written before it is read in every call
+ * and nothing about a call lives on the host, so a captured plan or deliver replays any number of times.
+ * Calls on different streams of one context are ordered by the library (they share the scratch); a
+ * graph launch is the caller's to order. wg_rx_reserve(ctx, max_packets): scratch for batches of up to
+ * max_packets; a call that needs more allocates it, except on a capturing stream (WG_EINVAL: reserve
+ * first). The table and the scratch are allocated at the first of these four calls: a context that
+ * never plans pays nothing. */
+#define WG_PKT_NOSESSION 10u /* transport packet whose receiver index is not in the session table */
+#define WG_PKT_HANDSHAKE 11u /* type 1 or 2: a handshake message, listed in host_list for the host */
+#define WG_RX_PT_AFTER 0u
+#define WG_RX_PT_PACKED 1u
+typedef struct wg_rx_summary {
+  uint64_t pt_used; /* PACKED: bytes of the plaintext ring this batch takes (may exceed what fits) */
+  uint32_t n_open;  /* packets with rx_status WG_PKT_OK */
+  uint32_t n_host;  /* entries of host_list */
+} wg_rx_summary;
+typedef struct wg_rx_batch {
+  const uint8_t* wire;     /* UDP ring (device) */
+  uint64_t wire_size;
+  const uint64_t* pkt_off; /* device, n entries */
+  const uint32_t* pkt_len; /* device, n entries */
+  wg_pkt* desc_out;        /* device, 16-byte aligned, n entries: for wg_open_batch */
+  uint32_t* rx_status;     /* device, n entries, WG_PKT_* */
+  uint32_t* host_list;     /* device, n entries: batch indices of handshake messages, ascending */
+  wg_rx_summary* summary;  /* device, 16 bytes */
+  uint64_t pt_base;        /* WG_RX_PT_PACKED: where this batch's plaintexts start in the open's output buffer */
+  uint64_t pt_size;        /* WG_RX_PT_PACKED: size of that buffer */
+  uint32_t n;
+  uint32_t max_len;
+  uint32_t mode;           /* WG_RX_PT_AFTER or WG_RX_PT_PACKED */
+  uint32_t _reserved;
+} wg_rx_batch;
+typedef struct wg_rx_item {
+  uint64_t off; /* of the plaintext in the open's output buffer (= desc.out_off) */
+  uint32_t len;
+  uint32_t key_slot;
+} wg_rx_item;
+typedef struct wg_rx_delivered {
+  uint64_t bytes;       /* sum of len over the items */
+  uint32_t n_items;
+  uint32_t n_keepalive; /* final status WG_PKT_KEEPALIVE */
+} wg_rx_delivered;
+typedef struct wg_rx_deliver_batch {
+  const wg_pkt* desc;          /* device, n entries: the plan's desc_out */
+  const uint32_t* plan_status; /* device, n entries: the plan's rx_status */
+  const uint32_t* open_status; /* device, n entries: the open's status after wg_rx_check */
+  uint32_t* final_status;      /* device, n entries */
+  wg_rx_item* items;           /* device, 16-byte aligned, n entries */
+  uint32_t* index_out;         /* device, n entries, or NULL */
+  wg_rx_delivered* delivered;  /* device, 16 bytes */
+  uint32_t n;
+  uint32_t _reserved;
+} wg_rx_deliver_batch;
+int wg_rx_sessions_set(wg_ctx* ctx, const uint32_t* indices_host, const uint32_t* key_slots_host, uint32_t n);
+int wg_rx_reserve(wg_ctx* ctx, uint32_t max_packets);
+int wg_rx_plan(wg_ctx* ctx, const wg_rx_batch* batch, void* stream);
+int wg_rx_deliver(wg_ctx* ctx, const wg_rx_deliver_batch* batch, void* stream);
+
 int wg_seal1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* pt, uint32_t len, uint8_t* out);
 int wg_open1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* in, uint32_t len, uint8_t* pt);
 int wg_pp_config(wg_ctx* ctx, uint32_t waves, uint32_t idle_us);

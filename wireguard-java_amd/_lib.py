@@ -32,12 +32,16 @@ WG_PKT_REPLAY = 6
 WG_PKT_NOKEY = 7
 WG_PKT_NOROUTE = 8
 WG_PKT_TOOLONG = 9
+WG_PKT_NOSESSION = 10
+WG_PKT_HANDSHAKE = 11
 WG_PKT_FAILED = 255
 WG_QUEUE_MAX_LEN = 16384
 WG_RX_FILTER = 1
 WG_RX_REPLAY = 2
 WG_TX_BROADCAST = 0
 WG_TX_ROUTE = 1
+WG_RX_PT_AFTER = 0
+WG_RX_PT_PACKED = 1
 WG_MAX_FILTERS = 65536
 WG_NO_FILTER = 0xFFFFFFFF
 WG_LEN_INVALID = 0xFFFFFFFF
@@ -96,6 +100,37 @@ class WgTxBatch(ctypes.Structure):
                 ("_reserved", ctypes.c_uint32)]
 
 
+class WgRxSummary(ctypes.Structure):
+    """wg_rx_summary: what wg_rx_plan leaves beside the descriptors."""
+    _fields_ = [("pt_used", ctypes.c_uint64), ("n_open", ctypes.c_uint32), ("n_host", ctypes.c_uint32)]
+
+
+class WgRxBatch(ctypes.Structure):
+    """wg_rx_batch: one wg_rx_plan call (device pointers)."""
+    _fields_ = [("wire", ctypes.c_void_p), ("wire_size", ctypes.c_uint64), ("pkt_off", ctypes.c_void_p),
+                ("pkt_len", ctypes.c_void_p), ("desc_out", ctypes.c_void_p), ("rx_status", ctypes.c_void_p),
+                ("host_list", ctypes.c_void_p), ("summary", ctypes.c_void_p), ("pt_base", ctypes.c_uint64),
+                ("pt_size", ctypes.c_uint64), ("n", ctypes.c_uint32), ("max_len", ctypes.c_uint32),
+                ("mode", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
+
+
+class WgRxItem(ctypes.Structure):
+    """wg_rx_item: one tun write of wg_rx_deliver's list."""
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint32), ("key_slot", ctypes.c_uint32)]
+
+
+class WgRxDelivered(ctypes.Structure):
+    """wg_rx_delivered: totals of one wg_rx_deliver call."""
+    _fields_ = [("bytes", ctypes.c_uint64), ("n_items", ctypes.c_uint32), ("n_keepalive", ctypes.c_uint32)]
+
+
+class WgRxDeliverBatch(ctypes.Structure):
+    """wg_rx_deliver_batch: one wg_rx_deliver call (device pointers)."""
+    _fields_ = [("desc", ctypes.c_void_p), ("plan_status", ctypes.c_void_p), ("open_status", ctypes.c_void_p),
+                ("final_status", ctypes.c_void_p), ("items", ctypes.c_void_p), ("index_out", ctypes.c_void_p),
+                ("delivered", ctypes.c_void_p), ("n", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
+
+
 class WgCompletion(ctypes.Structure):
     """wg_completion: one reaped packet of a wg_queue."""
     _fields_ = [("user", ctypes.c_uint64), ("counter", ctypes.c_uint64), ("data", ctypes.c_void_p),
@@ -111,6 +146,8 @@ class WgSubmit(ctypes.Structure):
 
 assert ctypes.sizeof(WgBatch) == 64 and ctypes.sizeof(WgCompletion) == 48 and ctypes.sizeof(WgSubmit) == 32
 assert ctypes.sizeof(WgTxBatch) == 88
+assert ctypes.sizeof(WgRxBatch) == 96 and ctypes.sizeof(WgRxDeliverBatch) == 64
+assert ctypes.sizeof(WgRxSummary) == 16 and ctypes.sizeof(WgRxItem) == 16 and ctypes.sizeof(WgRxDelivered) == 16
 assert ctypes.sizeof(WgPkt) == 32 and ctypes.sizeof(WgAeadDesc) == 64 and ctypes.sizeof(WgPrefix) == 18
 
 # (name, restype, argtypes) for every symbol include/wgaead.h declares
@@ -148,6 +185,10 @@ SIGNATURES = [
     ("wg_tx_counters_get", _I, [_VP, _U32, _U32, _VP]),
     ("wg_tx_reserve", _I, [_VP, _U32]),
     ("wg_tx_plan", _I, [_VP, ctypes.POINTER(WgTxBatch), _VP]),
+    ("wg_rx_sessions_set", _I, [_VP, _VP, _VP, _U32]),
+    ("wg_rx_reserve", _I, [_VP, _U32]),
+    ("wg_rx_plan", _I, [_VP, ctypes.POINTER(WgRxBatch), _VP]),
+    ("wg_rx_deliver", _I, [_VP, ctypes.POINTER(WgRxDeliverBatch), _VP]),
     ("wg_seal1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_open1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_pp_config", _I, [_VP, _U32, _U32]),

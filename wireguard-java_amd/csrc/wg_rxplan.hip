@@ -1,0 +1,554 @@
+// wg_rxplan.hip — receive-side planning around open, on the device (included by wg_capi.hip).
+//
+// The reference's inbound path decides three things per datagram on the host before it can decipher:
+// the packet class from the type byte (PacketElement.java:107-113: 1 initiation, 2 response, 4
+// transport, anything else throws), the peer of a transport packet's receiver index
+// (PeerList.java:53-67, an unknown index is dropped at :61-65) and that peer's session
+// (TransportManager.java:70-77, none: dropped at :73-77); UndecryptedIncomingTransport.java:20-33 then
+// cuts the packet into counter, ciphertext and the plaintext's place (:30). After decipher,
+// TransportManager.processDecryptedTransport (TransportManager.java:98-119) queues what goes to the tun
+// device, one packet at a time. wg_rx_plan does the first part for a whole UDP ring and writes the
+// wg_pkt descriptors wg_open_batch takes; wg_rx_deliver does the last and writes the list of tun
+// writes in arrival order. The host handles the handshake messages the plan lists, and nothing else.
+//
+// Sessions. receiver index -> key slot is an open-addressing hash table built on the host
+// (wg_rx_sessions_set): capacity = the smallest power of two >= max(16, 4 n), 8-B entries {index,
+// key slot + 1} (0: empty), bucket = mix(index) & mask with MurmurHash3's 32-bit finaliser as mix (the
+// reference's indices are 0, 1, 2, ..., WireGuard's are random, a test's may be multiples of anything: the
+// finaliser spreads them all), linear probing; at most a quarter full, so a probe sequence is short (a
+// wave walks as long as the longest of its 64) and ends at an empty entry. Its header sits at a fixed device address and names the
+// entries (the TxRouteHdr pattern of wg_tx.hip): a table change may move them, a captured plan reads
+// the header when it runs.
+//
+// Ranks. The plan needs two stable ranks over the batch (the handshake list, the 64-bit prefix of the
+// packed plaintext offsets) and the deliver one (the item list). Both run the same three launches on
+// the call's stream, with no wait between workgroups (no spin on another block's flag, no assumption
+// about dispatch order):
+//   k_rx_classify / k_rx_merge  one packet per thread, kRxRange = 256 packets per workgroup: the
+//                  checks (type byte, probe, header loads; the merge of the two statuses), the
+//                  packet's code to scratch so that none of it is done twice, and the workgroup's
+//                  sums {bytes, count, count} as ONE 16-B record of the partials array.
+//   k_rx_scan      one workgroup walks the partials in chunks of 256, replaces every record by the
+//                  exclusive prefix of the records before it, and writes the totals as the summary.
+//   k_rx_emit / k_rx_items  the same ranges: rank = the range's prefix + a ballot / scan inside the
+//                  workgroup; descriptors as two 16-B stores, items as one.
+// What one launch leaves for the next is ordered by the kernel boundary. Every scratch word (code,
+// partials) is written by the first launch of a call before a later one reads it, nothing is carried
+// from call to call and nothing about a call lives on the host, so a captured plan or deliver replays
+// any number of times. In packed mode a packet can fail only once its offset is known (it does not fit
+// pt_size), so n_open is summed by the emit launch: the scan writes it as 0 and every workgroup adds
+// its count with one atomic (a few hundred adds per 65,536 packets).
+#pragma once
+
+namespace {
+
+constexpr uint32_t kRxRange = 256;  // packets per workgroup of the classify / merge / emit / items launches
+
+struct RxSessHdr {  // at a fixed device address; a table change rewrites it (and may move the entries)
+  const uint2* entries;  // capacity x {index, key slot + 1 (0: empty)}
+  uint32_t mask;         // capacity - 1; bucket = rx_mix(index) & mask
+  uint32_t count;
+};
+
+// MurmurHash3's fmix32
+__host__ __device__ inline uint32_t rx_mix(uint32_t h) {
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+
+struct RxPlanState {
+  DevBuf d_hdr;    // RxSessHdr (fixed address)
+  DevBuf d_empty;  // 16 empty entries: the table of a context without sessions
+  DevBuf d_ent;    // the entries of the current table
+  DevBuf d_code;   // per packet: {status, key slot, counter lo, counter hi}
+  DevBuf d_part;   // per workgroup: {bytes lo, bytes hi, count, count}, then their exclusive prefixes
+  hipEvent_t ev = nullptr;  // last use of the table / scratch, and its stream
+  hipStream_t ev_stream = (hipStream_t)-1;
+};
+
+uint32_t rxp_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + kRxRange - 1u) / kRxRange); }
+
+void rxp_header(const RxPlanState* t, uint32_t n, bool own, RxSessHdr* H) {
+  uint32_t cap = 16;
+  while (own && (uint64_t)cap < 4ull * n) cap <<= 1;
+  H->entries = (const uint2*)(own ? t->d_ent.p : t->d_empty.p);
+  H->mask = cap - 1u;
+  H->count = own ? n : 0u;
+}
+
+// The receive-plan state, allocated at the first wg_rx_sessions_set / wg_rx_reserve / wg_rx_plan /
+// wg_rx_deliver call. Caller holds c->mu.
+int rxp_get(wg_ctx* c, RxPlanState** out) {
+  if (!c->rxp) {
+    auto t = std::make_unique<RxPlanState>();
+    int rc;
+    if ((rc = t->d_hdr.ensure(sizeof(RxSessHdr))) != WG_OK || (rc = t->d_empty.ensure(16 * sizeof(uint2))) != WG_OK) {
+      for (DevBuf* b : {&t->d_hdr, &t->d_empty}) b->release();
+      return rc;
+    }
+    RxSessHdr H;
+    rxp_header(t.get(), 0, false, &H);
+    hipError_t e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_empty.p, 0, 16 * sizeof(uint2), c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(t->d_hdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+      for (DevBuf* b : {&t->d_hdr, &t->d_empty}) b->release();
+      if (t->ev) (void)hipEventDestroy(t->ev);
+      return fail(WG_EDEVICE, "receive plan state: %s", hipGetErrorString(e));
+    }
+    c->rxp = t.release();
+  }
+  *out = c->rxp;
+  return WG_OK;
+}
+
+void rxp_free(wg_ctx* c) {
+  if (!c->rxp) return;
+  RxPlanState* t = c->rxp;
+  for (DevBuf* b : {&t->d_hdr, &t->d_empty, &t->d_ent, &t->d_code, &t->d_part}) b->release();
+  if (t->ev) (void)hipEventDestroy(t->ev);
+  delete t;
+  c->rxp = nullptr;
+}
+
+// Orders stream s behind the last plan / deliver / table write (which may sit on another stream), and
+// the next one behind what s does now. Caller holds c->mu.
+int rxp_after_last(RxPlanState* t, hipStream_t s) {
+  if (t->ev_stream != s && t->ev_stream != (hipStream_t)-1) HIPTRY(hipStreamWaitEvent(s, t->ev, 0));
+  return WG_OK;
+}
+int rxp_mark(RxPlanState* t, hipStream_t s) {
+  HIPTRY(hipEventRecord(t->ev, s));
+  t->ev_stream = s;
+  return WG_OK;
+}
+
+bool rxp_scratch_fits(const RxPlanState* t, uint32_t n) {
+  return (size_t)std::max(n, 1u) * 16 <= t->d_code.cap && (size_t)std::max(rxp_blocks(n), 1u) * 16 <= t->d_part.cap;
+}
+// scratch for batches of up to n packets; never on a capturing stream (the caller checks)
+int rxp_scratch(RxPlanState* t, uint32_t n) {
+  if (rxp_scratch_fits(t, n)) return WG_OK;
+  HIPTRY(hipDeviceSynchronize());  // the scratch is reallocated under earlier calls
+  int rc;
+  if ((rc = t->d_code.ensure((size_t)std::max(n, 1u) * 16)) != WG_OK ||
+      (rc = t->d_part.ensure((size_t)std::max(rxp_blocks(n), 1u) * 16)) != WG_OK)
+    return rc;
+  return WG_OK;
+}
+
+}  // namespace
+
+// ---- device -------------------------------------------------------------------------------
+namespace wgrp {
+
+struct RxPlanParams {
+  const uint8_t* wire;
+  uint64_t wire_size;
+  const uint64_t* pkt_off;
+  const uint32_t* pkt_len;
+  wg_pkt* desc;
+  uint32_t* status;
+  uint32_t* host_list;
+  wg_rx_summary* summary;
+  uint64_t pt_base;
+  uint64_t pt_room;  // packed: bytes from pt_base to the end of the buffer
+  uint32_t n, max_len, packed;
+  uint32_t pt_ok;    // packed: pt_base lies inside the buffer (otherwise nothing fits, not even a keepalive)
+  const RxSessHdr* sessions;
+  uint4* code;
+  uint4* part;
+};
+
+struct RxDeliverParams {
+  const wg_pkt* desc;
+  const uint32_t* plan_status;
+  const uint32_t* open_status;
+  uint32_t* final_status;
+  wg_rx_item* items;
+  uint32_t* index_out;
+  wg_rx_delivered* delivered;
+  uint32_t n;
+  uint4* part;
+};
+
+__device__ __forceinline__ uint64_t u64_of(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
+
+__device__ __forceinline__ uint64_t shfl_up64(uint64_t v, uint32_t d) {
+  const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d), hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d);
+  return u64_of(lo, hi);
+}
+
+// Over the 256 threads of the workgroup, in thread order: the flagged threads below me (rank) and in
+// all (total). Every thread must reach the call; `wsum` is 4 words of LDS of this call's own.
+__device__ __forceinline__ void block_rank(bool flag, uint32_t* wsum, uint32_t& rank, uint32_t& total) {
+  const uint64_t m = __ballot(flag);
+  const uint32_t w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63u) == 0) wsum[w] = (uint32_t)__popcll((unsigned long long)m);
+  __syncthreads();
+  rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+  total = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 4; ++k) {
+    const uint32_t x = wsum[k];
+    rank += k < w ? x : 0u;
+    total += x;
+  }
+}
+
+// The same for a 64-bit value: the sum of v over the threads below me (excl) and over all (total).
+__device__ __forceinline__ void block_scan64(uint64_t v, uint64_t* wsum, uint64_t& excl, uint64_t& total) {
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  uint64_t inc = v;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint64_t up = shfl_up64(inc, d);
+    if (lane >= d) inc += up;
+  }
+  if (lane == 63u) wsum[w] = inc;
+  __syncthreads();
+  excl = inc - v;
+  total = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 4; ++k) {
+    const uint64_t x = wsum[k];
+    excl += k < w ? x : 0ull;
+    total += x;
+  }
+}
+
+// key slot + 1 of a receiver index, 0 if the table does not hold it. Two entries of the probe sequence
+// are fetched per round trip (each one 8-B load): a wave walks as long as its longest chain.
+__device__ __forceinline__ uint32_t rx_session(const RxSessHdr& H, uint32_t index) {
+  const uint64_t* ent = (const uint64_t*)H.entries;  // {index, key slot + 1} = low, high word
+  uint32_t b = rx_mix(index);
+  for (uint32_t probes = 0; probes <= H.mask; probes += 2u) {  // (a table a quarter full ends the walk long before)
+    const uint64_t e0 = ent[b & H.mask], e1 = ent[(b + 1u) & H.mask];
+    if (!(uint32_t)(e0 >> 32)) return 0u;
+    if ((uint32_t)e0 == index) return (uint32_t)(e0 >> 32);
+    if (!(uint32_t)(e1 >> 32)) return 0u;
+    if ((uint32_t)e1 == index) return (uint32_t)(e1 >> 32);
+    b += 2u;
+  }
+  return 0u;
+}
+
+// Steps 1-5 of wg_rx_plan and, in AFTER mode, step 6; writes the packet's code and the range's sums.
+__global__ void __launch_bounds__(256) k_rx_classify(RxPlanParams P) {
+  __shared__ uint32_t s_cnt[2][4];
+  __shared__ uint64_t s_sum[4];
+  const uint32_t i = blockIdx.x * kRxRange + threadIdx.x;
+  const bool in = i < P.n;
+  const RxSessHdr H = *P.sessions;
+  uint32_t st = WG_PKT_BADHDR, slot = 0, len = 0, c_lo = 0, c_hi = 0;
+  if (in) {
+    const uint64_t o = P.pkt_off[i];
+    const uint32_t wl = P.pkt_len[i];
+    if (wl != 0 && o <= P.wire_size && (uint64_t)wl <= P.wire_size - o) {
+      const uint8_t* h = P.wire + o;
+      // the whole header in one round trip where the packet holds one (a shorter one: its type byte)
+      uint32_t w[4] = {0u, 0u, 0u, 0u};
+      if (wl >= 16u) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[k] = wgt::load_u32_any(h + 4 * k);
+      } else {
+        w[0] = h[0];
+      }
+      const uint32_t t = w[0] & 0xffu;
+      if (t == 1u || t == 2u) {
+        st = WG_PKT_HANDSHAKE;
+      } else if (t == 4u && wl >= 32u) {
+        const uint32_t hit = rx_session(H, w[1]);
+        len = wl - 32u;
+        if (!hit) {
+          st = WG_PKT_NOSESSION;
+        } else {
+          slot = hit - 1u;
+          if (len > P.max_len) st = WG_PKT_TOOLONG;
+          else if (!P.packed && (uint64_t)len > P.wire_size - o - wl) st = WG_PKT_BADHDR;  // the plaintext overruns the ring
+          else {
+            st = WG_PKT_OK;
+            c_lo = w[2];
+            c_hi = w[3];
+          }
+        }
+      }
+    }
+    P.code[i] = make_uint4(st, slot, c_lo, c_hi);
+  }
+  const bool ok = in && st == WG_PKT_OK;
+  uint32_t r0, r1, n_ok, n_host;
+  uint64_t ex, bytes;
+  block_rank(ok && !P.packed, s_cnt[0], r0, n_ok);
+  block_rank(in && st == WG_PKT_HANDSHAKE, s_cnt[1], r1, n_host);
+  block_scan64(ok && P.packed ? ((uint64_t)len + 15u) & ~15ull : 0ull, s_sum, ex, bytes);
+  if (threadIdx.x == 0) P.part[blockIdx.x] = make_uint4((uint32_t)bytes, (uint32_t)(bytes >> 32), n_ok, n_host);
+}
+
+// Exclusive prefixes of the per-range records, in place, and the totals as the 16-B summary
+// {bytes, count, count} (wg_rx_summary / wg_rx_delivered). One workgroup.
+__global__ void __launch_bounds__(256) k_rx_scan(uint4* part, uint32_t nb, uint2* summary) {
+  __shared__ uint64_t s_sum[4];
+  uint64_t run_bytes = 0;
+  uint32_t run_a = 0, run_b = 0;
+  for (uint32_t b0 = 0; b0 < nb; b0 += 256u) {  // (workgroup-uniform trips)
+    const uint32_t b = b0 + threadIdx.x;
+    const uint4 v = b < nb ? part[b] : make_uint4(0u, 0u, 0u, 0u);
+    // counts of one range are <= 256: their scans run as 64-bit sums of a packed pair
+    uint64_t ex, tot, exc, totc;
+    block_scan64(u64_of(v.x, v.y), s_sum, ex, tot);
+    __syncthreads();  // s_sum is read by every thread before the next scan writes it
+    block_scan64(u64_of(v.z, v.w), s_sum, exc, totc);
+    __syncthreads();
+    if (b < nb) {
+      const uint64_t pb = run_bytes + ex;
+      part[b] = make_uint4((uint32_t)pb, (uint32_t)(pb >> 32), run_a + (uint32_t)exc, run_b + (uint32_t)(exc >> 32));
+    }
+    run_bytes += tot;
+    run_a += (uint32_t)totc;
+    run_b += (uint32_t)(totc >> 32);
+  }
+  if (threadIdx.x == 0) {  // (8-B stores: the summary need not be 16-B aligned)
+    summary[0] = make_uint2((uint32_t)run_bytes, (uint32_t)(run_bytes >> 32));
+    summary[1] = make_uint2(run_a, run_b);
+  }
+}
+
+__global__ void __launch_bounds__(256) k_rx_emit(RxPlanParams P) {
+  __shared__ uint32_t s_cnt[2][4];
+  __shared__ uint64_t s_sum[4];
+  const uint32_t i = blockIdx.x * kRxRange + threadIdx.x;
+  const bool in = i < P.n;
+  const uint4 c = in ? P.code[i] : make_uint4(WG_PKT_BADHDR, 0u, 0u, 0u);
+  const uint64_t o = in ? P.pkt_off[i] : 0ull;
+  const uint32_t wl = in ? P.pkt_len[i] : 0u;
+  const uint4 pre = P.part[blockIdx.x];
+  uint32_t st = c.x;
+  const uint32_t len = wl - 32u;  // (meaningful where the code is WG_PKT_OK)
+  const bool pass = in && st == WG_PKT_OK;
+  uint64_t ex, tot;
+  block_scan64(pass && P.packed ? ((uint64_t)len + 15u) & ~15ull : 0ull, s_sum, ex, tot);
+  uint64_t out_off = P.packed ? P.pt_base : o + wl;
+  if (pass && P.packed) {
+    const uint64_t C = u64_of(pre.x, pre.y) + ex;
+    if (P.pt_ok && C <= P.pt_room && (uint64_t)len <= P.pt_room - C) out_off = P.pt_base + C;
+    else st = WG_PKT_TOOLONG;
+  }
+  const bool ok = in && st == WG_PKT_OK;
+  uint32_t hr, n_host, kr, n_ok;
+  block_rank(in && st == WG_PKT_HANDSHAKE, s_cnt[0], hr, n_host);
+  block_rank(ok, s_cnt[1], kr, n_ok);
+  if (P.packed && threadIdx.x == 0 && n_ok) atomicAdd(&P.summary->n_open, n_ok);
+  if (!in) return;
+  const uint64_t in_off = o + 16u;
+  uint4* d = (uint4*)(P.desc + i);
+  d[0] = make_uint4((uint32_t)in_off, (uint32_t)(in_off >> 32), (uint32_t)out_off, (uint32_t)(out_off >> 32));
+  d[1] = ok ? make_uint4(c.z, c.w, len, c.y) : make_uint4(0u, 0u, WG_LEN_INVALID, c.y);
+  P.status[i] = st;
+  if (st == WG_PKT_HANDSHAKE) P.host_list[pre.w + hr] = i;
+}
+
+// final status = the plan's unless that is WG_PKT_OK, then the open's; the range's sums
+__global__ void __launch_bounds__(256) k_rx_merge(RxDeliverParams P) {
+  __shared__ uint32_t s_cnt[2][4];
+  __shared__ uint64_t s_sum[4];
+  const uint32_t i = blockIdx.x * kRxRange + threadIdx.x;
+  const bool in = i < P.n;
+  uint32_t st = WG_PKT_BADHDR, len = 0;
+  if (in) {
+    const uint32_t ps = P.plan_status[i];
+    st = ps != WG_PKT_OK ? ps : P.open_status[i];
+    P.final_status[i] = st;
+    if (st == WG_PKT_OK) len = P.desc[i].len;
+  }
+  uint32_t r0, r1, n_items, n_keep;
+  uint64_t ex, bytes;
+  block_rank(in && st == WG_PKT_OK, s_cnt[0], r0, n_items);
+  block_rank(in && st == WG_PKT_KEEPALIVE, s_cnt[1], r1, n_keep);
+  block_scan64((uint64_t)len, s_sum, ex, bytes);
+  if (threadIdx.x == 0) P.part[blockIdx.x] = make_uint4((uint32_t)bytes, (uint32_t)(bytes >> 32), n_items, n_keep);
+}
+
+__global__ void __launch_bounds__(256) k_rx_items(RxDeliverParams P) {
+  __shared__ uint32_t s_cnt[4];
+  const uint32_t i = blockIdx.x * kRxRange + threadIdx.x;
+  const bool in = i < P.n;
+  const bool ok = in && P.final_status[i] == WG_PKT_OK;
+  const uint4 pre = P.part[blockIdx.x];
+  uint32_t r, total;
+  block_rank(ok, s_cnt, r, total);
+  if (!ok) return;
+  const uint4* d = (const uint4*)(P.desc + i);
+  const uint4 a = d[0], b = d[1];
+  const uint32_t j = pre.z + r;
+  *(uint4*)(P.items + j) = make_uint4(a.z, a.w, b.z, b.w);
+  if (P.index_out) P.index_out[j] = i;
+}
+
+}  // namespace wgrp
+
+// ---- C ABI --------------------------------------------------------------------------------
+extern "C" {
+
+int wg_rx_sessions_set(wg_ctx* c, const uint32_t* indices, const uint32_t* slots, uint32_t n) {
+  if (!c || ((!indices || !slots) && n)) return fail(WG_EINVAL, "NULL argument");
+  if (n > 0x20000000u) return fail(WG_E2BIG, "session table of %u entries", n);
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  RxPlanState* t;
+  int rc;
+  if ((rc = rxp_get(c, &t)) != WG_OK) return rc;
+  RxSessHdr H;
+  rxp_header(t, n, n != 0, &H);
+  std::vector<uint2> ent(n ? (size_t)H.mask + 1 : 0, make_uint2(0u, 0u));
+  for (uint32_t k = 0; k < n; ++k) {
+    if (slots[k] >= c->key_slots) return fail(WG_ERANGE, "session %u: key slot %u >= %u", k, slots[k], c->key_slots);
+    uint32_t b = rx_mix(indices[k]) & H.mask;
+    while (ent[b].y) {
+      if (ent[b].x == indices[k]) return fail(WG_EINVAL, "session %u: receiver index 0x%08x repeats", k, indices[k]);
+      b = (b + 1u) & H.mask;
+    }
+    ent[b] = make_uint2(indices[k], slots[k] + 1u);
+  }
+  HIPTRY(hipDeviceSynchronize());  // the entries may move: no plan launched earlier (on any stream) may still read them
+  if (n) {
+    if ((rc = t->d_ent.ensure(ent.size() * sizeof(uint2))) != WG_OK) {
+      rxp_header(t, 0, false, &H);  // the old entries are gone: no sessions
+      (void)hipMemcpyAsync(t->d_hdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream);
+      (void)hipStreamSynchronize(c->stream);
+      return rc;
+    }
+    H.entries = (const uint2*)t->d_ent.p;
+    HIPTRY(hipMemcpyAsync(t->d_ent.p, ent.data(), ent.size() * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPTRY(hipMemcpyAsync(t->d_hdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream));
+  if ((rc = rxp_mark(t, c->stream)) != WG_OK) return rc;
+  HIPTRY(hipStreamSynchronize(c->stream));
+  return WG_OK;
+}
+
+int wg_rx_reserve(wg_ctx* c, uint32_t max_packets) {
+  if (!c) return fail(WG_EINVAL, "NULL context");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  RxPlanState* t;
+  int rc;
+  if ((rc = rxp_get(c, &t)) != WG_OK) return rc;
+  return rxp_scratch(t, max_packets);
+}
+
+int wg_rx_plan(wg_ctx* c, const wg_rx_batch* b, void* stream) {
+  if (!c || !b) return fail(WG_EINVAL, "NULL argument");
+  if (b->mode != WG_RX_PT_AFTER && b->mode != WG_RX_PT_PACKED) return fail(WG_EINVAL, "unknown receive mode %u", b->mode);
+  if (b->_reserved) return fail(WG_EINVAL, "wg_rx_batch._reserved must be 0");
+  if (!b->summary || (((uintptr_t)b->summary) & 7u)) return fail(WG_EINVAL, "summary must be non-NULL and 8-byte aligned");
+  hipStream_t s = pick_stream(c, stream);
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  const bool capturing = tx_capturing(s);
+  if (capturing && !c->rxp)
+    return fail(WG_EINVAL, "receive plan on a capturing stream before any wg_rx_* planning call: call wg_rx_reserve first");
+  RxPlanState* t;
+  int rc;
+  if ((rc = rxp_get(c, &t)) != WG_OK) return rc;
+  const uint32_t n = b->n;
+  if (n == 0) {
+    HIPTRY(hipMemsetAsync(b->summary, 0, sizeof(wg_rx_summary), s));
+    return WG_OK;
+  }
+  if (!b->wire || !b->pkt_off || !b->pkt_len) return fail(WG_EINVAL, "NULL wire ring or packet table");
+  if (!b->desc_out || (((uintptr_t)b->desc_out) & 15u) || !b->rx_status || (((uintptr_t)b->rx_status) & 3u) ||
+      !b->host_list || (((uintptr_t)b->host_list) & 3u))
+    return fail(WG_EINVAL, "descriptor / status / host list output must be non-NULL and aligned (16 / 4 / 4 bytes)");
+  if (capturing) {
+    if (!rxp_scratch_fits(t, n))
+      return fail(WG_EINVAL, "receive plan of %u packets on a capturing stream needs more scratch: call wg_rx_reserve(%u) first", n, n);
+  } else {
+    if ((rc = rxp_scratch(t, n)) != WG_OK) return rc;
+    if ((rc = rxp_after_last(t, s)) != WG_OK) return rc;
+  }
+  wgrp::RxPlanParams P{};
+  P.wire = b->wire;
+  P.wire_size = b->wire_size;
+  P.pkt_off = b->pkt_off;
+  P.pkt_len = b->pkt_len;
+  P.desc = b->desc_out;
+  P.status = b->rx_status;
+  P.host_list = b->host_list;
+  P.summary = b->summary;
+  P.packed = b->mode == WG_RX_PT_PACKED ? 1u : 0u;
+  P.pt_base = P.packed ? b->pt_base : 0;
+  P.pt_ok = (P.packed && b->pt_base <= b->pt_size) ? 1u : 0u;
+  P.pt_room = P.pt_ok ? b->pt_size - b->pt_base : 0;
+  P.n = n;
+  P.max_len = b->max_len;
+  P.sessions = (const RxSessHdr*)t->d_hdr.p;
+  P.code = (uint4*)t->d_code.p;
+  P.part = (uint4*)t->d_part.p;
+  const uint32_t nb = rxp_blocks(n);
+  hipLaunchKernelGGL(wgrp::k_rx_classify, dim3(nb), dim3(256), 0, s, P);
+  hipLaunchKernelGGL(wgrp::k_rx_scan, dim3(1), dim3(256), 0, s, P.part, nb, (uint2*)b->summary);
+  hipLaunchKernelGGL(wgrp::k_rx_emit, dim3(nb), dim3(256), 0, s, P);
+  const hipError_t le = hipGetLastError();
+  if (le != hipSuccess) return fail(WG_EDEVICE, "receive plan kernels: %s", hipGetErrorString(le));
+  if (!capturing && (rc = rxp_mark(t, s)) != WG_OK) return rc;
+  return WG_OK;
+}
+
+int wg_rx_deliver(wg_ctx* c, const wg_rx_deliver_batch* b, void* stream) {
+  if (!c || !b) return fail(WG_EINVAL, "NULL argument");
+  if (b->_reserved) return fail(WG_EINVAL, "wg_rx_deliver_batch._reserved must be 0");
+  if (!b->delivered || (((uintptr_t)b->delivered) & 7u)) return fail(WG_EINVAL, "delivered must be non-NULL and 8-byte aligned");
+  hipStream_t s = pick_stream(c, stream);
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  const bool capturing = tx_capturing(s);
+  if (capturing && !c->rxp)
+    return fail(WG_EINVAL, "receive deliver on a capturing stream before any wg_rx_* planning call: call wg_rx_reserve first");
+  RxPlanState* t;
+  int rc;
+  if ((rc = rxp_get(c, &t)) != WG_OK) return rc;
+  const uint32_t n = b->n;
+  if (n == 0) {
+    HIPTRY(hipMemsetAsync(b->delivered, 0, sizeof(wg_rx_delivered), s));
+    return WG_OK;
+  }
+  if (!b->desc || (((uintptr_t)b->desc) & 15u) || !b->plan_status || !b->open_status || !b->final_status)
+    return fail(WG_EINVAL, "NULL (or unaligned) descriptor or status array");
+  if (b->final_status == b->plan_status || b->final_status == b->open_status)
+    return fail(WG_EINVAL, "final_status may alias neither plan_status nor open_status");
+  if (!b->items || (((uintptr_t)b->items) & 15u) || (((uintptr_t)b->index_out) & 3u))
+    return fail(WG_EINVAL, "items must be non-NULL and 16-byte aligned (index_out: 4-byte)");
+  if (capturing) {
+    if (!rxp_scratch_fits(t, n))
+      return fail(WG_EINVAL, "receive deliver of %u packets on a capturing stream needs more scratch: call wg_rx_reserve(%u) first", n, n);
+  } else {
+    if ((rc = rxp_scratch(t, n)) != WG_OK) return rc;
+    if ((rc = rxp_after_last(t, s)) != WG_OK) return rc;
+  }
+  wgrp::RxDeliverParams P{};
+  P.desc = b->desc;
+  P.plan_status = b->plan_status;
+  P.open_status = b->open_status;
+  P.final_status = b->final_status;
+  P.items = b->items;
+  P.index_out = b->index_out;
+  P.delivered = b->delivered;
+  P.n = n;
+  P.part = (uint4*)t->d_part.p;
+  const uint32_t nb = rxp_blocks(n);
+  hipLaunchKernelGGL(wgrp::k_rx_merge, dim3(nb), dim3(256), 0, s, P);
+  hipLaunchKernelGGL(wgrp::k_rx_scan, dim3(1), dim3(256), 0, s, P.part, nb, (uint2*)b->delivered);
+  hipLaunchKernelGGL(wgrp::k_rx_items, dim3(nb), dim3(256), 0, s, P);
+  const hipError_t le = hipGetLastError();
+  if (le != hipSuccess) return fail(WG_EDEVICE, "receive deliver kernels: %s", hipGetErrorString(le));
+  if (!capturing && (rc = rxp_mark(t, s)) != WG_OK) return rc;
+  return WG_OK;
+}
+
+}  // extern "C"

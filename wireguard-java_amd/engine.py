@@ -275,6 +275,59 @@ class Engine:
                      wire_base=wire_base, stream=st)
         self.seal(desc_out, tun, out, max_len, uniform=uniform, stream=st, frame=True)
 
+    # ---- receive side around open (wg_rx_plan / wg_rx_deliver) ---------------------------
+    def rx_sessions_set(self, indices, key_slots) -> None:
+        """wg_rx_sessions_set: the whole receiver index -> key slot table (PeerList.java:53-67,
+        TransportManager.java:70-77); an empty list clears it."""
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint32))
+        ks = np.ascontiguousarray(np.asarray(key_slots, dtype=np.uint32))
+        if len(idx) != len(ks):
+            raise L.WgError(L.WG_EINVAL, f"{len(idx)} receiver indices for {len(ks)} key slots")
+        L.check(self._lib.wg_rx_sessions_set(self.ctx, idx.ctypes.data, ks.ctypes.data, len(idx)))
+
+    def rx_reserve(self, max_packets: int) -> None:
+        """wg_rx_reserve: scratch for receive plans / delivers of up to max_packets packets (needed before
+        one is captured into a graph: a capturing stream cannot allocate)."""
+        L.check(self._lib.wg_rx_reserve(self.ctx, max_packets))
+
+    def rx_plan(self, wire, pkt_off, pkt_len, desc_out, rx_status, host_list, summary, max_len: int,
+                packed: bool = False, pt_base: int = 0, pt_size: int = 0, stream: int | None = None) -> None:
+        """wg_rx_plan over torch tensors: wire uint8 UDP ring, pkt_off int64 [n], pkt_len int32 [n], desc_out
+        int64 [n, 4] (wg_pkt records for open()), rx_status / host_list int32 [n], summary int64 [2]
+        (wg_rx_summary: pt_used, n_open | n_host << 32). packed=False puts every plaintext right after its
+        packet in `wire` (the reference's layout); packed=True packs them, 16-B aligned, from pt_base of the
+        open's output buffer of pt_size bytes."""
+        b = L.WgRxBatch(wire.data_ptr(), wire.numel(), pkt_off.data_ptr(), pkt_len.data_ptr(), desc_out.data_ptr(),
+                        rx_status.data_ptr(), host_list.data_ptr(), summary.data_ptr(), pt_base, pt_size,
+                        pkt_off.shape[0], max_len, L.WG_RX_PT_PACKED if packed else L.WG_RX_PT_AFTER, 0)
+        L.check(self._lib.wg_rx_plan(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def rx_deliver(self, desc, plan_status, open_status, final_status, items, delivered, index_out=None,
+                   stream: int | None = None) -> None:
+        """wg_rx_deliver over torch tensors: final_status int32 [n], items int64 [n, 2] (wg_rx_item: off,
+        len | key_slot << 32), delivered int64 [2] (wg_rx_delivered: bytes, n_items | n_keepalive << 32),
+        index_out int32 [n] or None."""
+        b = L.WgRxDeliverBatch(desc.data_ptr(), plan_status.data_ptr(), open_status.data_ptr(),
+                               final_status.data_ptr(), items.data_ptr(),
+                               index_out.data_ptr() if index_out is not None else None, delivered.data_ptr(),
+                               desc.shape[0], 0)
+        L.check(self._lib.wg_rx_deliver(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def rx_open(self, wire, pkt_off, pkt_len, desc_out, rx_status, host_list, summary, out, open_status,
+                final_status, items, delivered, max_len: int, packed: bool = True, pt_base: int = 0,
+                index_out=None, replay: bool = False, uniform: bool = False, stream: int | None = None) -> None:
+        """UDP ring -> plaintext ring and tun list on one stream, the mirror of tx_seal: rx_plan, then
+        open(desc_out, wire, out, open_status, rx_filter=True), rx_check(WG_RX_REPLAY) if `replay`, then
+        rx_deliver. packed=False needs out to be the wire ring itself (plaintext after each packet)."""
+        st = stream if stream is not None else _torch_stream()
+        self.rx_plan(wire, pkt_off, pkt_len, desc_out, rx_status, host_list, summary, max_len, packed=packed,
+                     pt_base=pt_base, pt_size=out.numel(), stream=st)
+        self.open(desc_out, wire, out, open_status, max_len, uniform=uniform, stream=st, rx_filter=True)
+        if replay:
+            self.rx_check(desc_out, out, open_status, L.WG_RX_REPLAY, stream=st)
+        self.rx_deliver(desc_out, rx_status, open_status, final_status, items, delivered, index_out=index_out,
+                        stream=st)
+
     def set_receivers(self, receivers) -> None:
         """wg_ctx_set_receivers: device tensor of receiver_index per key slot for
         seal(..., frame=True) — contiguous, 4-byte integers, on this engine's device, at

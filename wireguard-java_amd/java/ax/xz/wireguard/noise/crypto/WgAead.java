@@ -36,13 +36,18 @@ public final class WgAead {
 	/** wg_tx_plan outcomes beside WG_PKT_OK / WG_PKT_BADIP: no route covers the destination; the packet or its wire slot does not fit. */
 	public static final int WG_PKT_NOROUTE = 8, WG_PKT_TOOLONG = 9;
 	public static final int WG_TX_BROADCAST = 0, WG_TX_ROUTE = 1;
-	public static final long AEAD_DESC_SIZE = 64, PKT_DESC_SIZE = 32, BATCH_SIZE = 64, TX_BATCH_SIZE = 88;
+	/** wg_rx_plan outcomes beside WG_PKT_OK / WG_PKT_BADHDR / WG_PKT_TOOLONG: no session for the receiver index; a handshake message for the host. */
+	public static final int WG_PKT_NOSESSION = 10, WG_PKT_HANDSHAKE = 11;
+	public static final int WG_RX_PT_AFTER = 0, WG_RX_PT_PACKED = 1;
+	public static final long AEAD_DESC_SIZE = 64, PKT_DESC_SIZE = 32, BATCH_SIZE = 64, TX_BATCH_SIZE = 88,
+		RX_BATCH_SIZE = 96, RX_DELIVER_BATCH_SIZE = 64, RX_SUMMARY_SIZE = 16, RX_ITEM_SIZE = 16, RX_DELIVERED_SIZE = 16;
 
 	static final MethodHandle SELFTEST, CTX_CREATE, LAST_ERROR, KEYS_SET, KEYS_ZERO, SEAL1, OPEN1, AEAD_HOST,
 		SEAL_BATCH, OPEN_BATCH, SYNC, SEAL_HOST, OPEN_HOST, HOST_ALLOC, HOST_FREE, FRAME_SEAL, PARSE_OPEN,
 		FILTER_SET, SLOT_FILTERS_SET, REPLAY_ENABLE, REPLAY_RESET, RX_CHECK, DUPLEX_BATCH, QUEUE_CREATE,
 		QUEUE_DESTROY, SUBMIT_SEAL, SUBMIT_OPEN, SUBMIT_SEAL_N, SUBMIT_OPEN_N, REAP, REAP_DONE, QUEUE_SUBMIT_TIMEOUT,
-		NUMA_NODE, TX_PEERS_SET, ROUTES_SET, TX_COUNTERS_SET, TX_COUNTERS_GET, TX_RESERVE, TX_PLAN;
+		NUMA_NODE, TX_PEERS_SET, ROUTES_SET, TX_COUNTERS_SET, TX_COUNTERS_GET, TX_RESERVE, TX_PLAN,
+		RX_SESSIONS_SET, RX_RESERVE, RX_PLAN, RX_DELIVER;
 
 	/** The process-wide context (one HIP device, its stream and its device key table). */
 	static final MemorySegment CTX;
@@ -103,6 +108,14 @@ public final class WgAead {
 			JAVA_INT, ADDRESS));
 		TX_RESERVE = down(linker, symbols, "wg_tx_reserve", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT));
 		TX_PLAN = down(linker, symbols, "wg_tx_plan", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
+		// receive side around open: sessions by receiver index, open descriptors, the tun delivery list
+		// (PacketElement.java:107-113, PeerList.java:53-67, TransportManager.java:70-77,:98-119); wg_rx_plan takes
+		// one wg_rx_batch struct of 96 bytes, wg_rx_deliver one wg_rx_deliver_batch struct of 64 bytes
+		RX_SESSIONS_SET = down(linker, symbols, "wg_rx_sessions_set", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS,
+			ADDRESS, JAVA_INT));
+		RX_RESERVE = down(linker, symbols, "wg_rx_reserve", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT));
+		RX_PLAN = down(linker, symbols, "wg_rx_plan", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
+		RX_DELIVER = down(linker, symbols, "wg_rx_deliver", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
 		// outgoing seal + incoming open in one launch (two wg_batch structs of 64 bytes)
 		DUPLEX_BATCH = down(linker, symbols, "wg_duplex_batch", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS,
 			ADDRESS));
