@@ -547,6 +547,105 @@ int wg_rx_reserve(wg_ctx* ctx, uint32_t max_packets);
 int wg_rx_plan(wg_ctx* ctx, const wg_rx_batch* batch, void* stream);
 int wg_rx_deliver(wg_ctx* ctx, const wg_rx_deliver_batch* batch, void* stream);
 
+/* ---- handshake admission: batched BLAKE2s, mac1 and mac2 on the device ----
+ * The device counterpart of the first thing the reference does with an incoming initiation or response,
+ * before any Noise work (IncomingInitiation.java:24-40, IncomingResponse.java:20-36): mac1 =
+ * BLAKE2s-128(key = BLAKE2s-256("mac1----" || local static public key), the message without its two
+ * MACs) (InitiationPacket.calculateMac1, InitiationPacket.java:110-120; ResponsePacket.java:107-117) must
+ * equal the message's mac1 field, and its mac2 field must be all zero (IncomingInitiation.java:38-40:
+ * cookies are not implemented). wg_rx_plan lists the handshake datagrams of a UDP ring; wg_hs_check
+ * tests them where they lie and compacts the accepted ones into records, so the host copies back
+ * 16 + 160 n_valid bytes and starts Noise on those; it never fetches the ring. X25519, the Noise state
+ * machine, cookies and timers stay on the host.
+ *
+ * wg_blake2s_batch(ctx, desc, n, in, in_size, out, out_size, status, stream): BLAKE2s (RFC 7693),
+ *   sequential mode, fanout 1, depth 1, parameter word outlen | keylen << 8 | 0x01010000
+ *   (Blake2s.java:94). out[out_off .. out_off + outlen) = the digest of size outlen of in[in_off ..
+ *   in_off + len) under the key in[key_off .. key_off + keylen) (keylen 0: unkeyed): what
+ *   Crypto.BLAKE2s256 and new Blake2s(n, key) compute. Every offset may have any alignment. status[i] is
+ *   WG_B2S_OK, or WG_B2S_BADDESC when outlen is 0 or above 32, keylen above 32, or one of the three
+ *   ranges leaves its buffer (each tested as off <= size && len <= size - off, which cannot overflow;
+ *   the key range of an unkeyed descriptor is the empty range at key_off); a BADDESC leaves the output
+ *   untouched. desc: device, 16-byte aligned. n = 0 is a no-op; out must not overlap in (WG_EINVAL).
+ *   Asynchronous on `stream`, no host state, can be captured. The kernel reads the input as aligned
+ *   32-bit words: those that hold at least one byte of a range, never another.
+ *
+ * wg_hs_key_set(ctx, static_public): derives the mac1 key of the local static public key, on the
+ *   device (the library has no host hash), into a 32-byte device buffer that keeps its address for the
+ *   life of the context: a captured check reads the key when it runs, so a new key needs no re-capture.
+ *   Synchronous, and ordered after every check queued before it, like wg_rx_sessions_set. The key is
+ *   wiped by wg_ctx_destroy. wg_hs_check without a key returns WG_ENOKEY.
+ *
+ * wg_hs_check(ctx, b, stream): wire / wire_size / pkt_off / pkt_len / n as in wg_rx_batch. list is a
+ *   device array of batch indices (the plan's host_list) and n_list a device pointer to its length
+ *   (&summary->n_host of the plan); the length is read on the device (at most n entries are looked
+ *   at), so nothing is synchronised between plan and check. list = NULL (then n_list must be NULL too)
+ *   is the identity list: every one of the n datagrams. For list position k, i = list[k], o =
+ *   pkt_off[i], wl = pkt_len[i], in this order:
+ *   1. i >= n, wl == 0, o > wire_size or wl > wire_size - o: WG_HS_BADLEN.
+ *   2. t = wire[o] is neither 1 nor 2: WG_HS_BADTYPE (only a caller-made or the identity list gets here).
+ *   3. wl != L, L = 148 for t = 1 and 92 for t = 2 (InitiationPacket.HEADER_LAYOUT,
+ *      ResponsePacket.HEADER_LAYOUT): WG_HS_BADLEN. The reference never looks at the received length of
+ *      a handshake message: it reads the layout out of a pooled buffer (PacketElement.java:102-113),
+ *      whatever was received. That cannot be restated over a ring; WireGuard's own rule, the exact
+ *      size, is applied instead.
+ *   4. BLAKE2s-128(mac1 key, msg[0 .. L - 32)) != msg[L - 32 .. L - 16): WG_HS_BADMAC1. All 16 bytes
+ *      are compared, without an early exit.
+ *   5. msg[L - 16 .. L) is not all zero: WG_HS_BADMAC2.
+ *   6. WG_HS_OK.
+ *   hs_status[k] is written for every k < the list's length and nothing behind it. records[0 ..
+ *   n_valid) is the stable compaction, in list order, of the WG_HS_OK messages: {index = i, len = L,
+ *   msg = the message, zero-filled behind a response, _pad = 0}; every byte of a written record is
+ *   defined and nothing behind n_valid records is touched. summary = {n_valid, n_init, n_resp (the
+ *   accepted messages of type 1 / 2), n_rejected}. n = 0 writes only the summary (zeros). records:
+ *   16-byte aligned; summary: 8-byte aligned. The rank takes three launches (check, scan, emit) with no
+ *   wait between workgroups; the scratch is written before it is read in every call and nothing about a
+ *   call lives on the host, so a captured plan + check replays. Calls on different streams of one
+ *   context are ordered by the library; a graph launch is the caller's to order.
+ *   wg_hs_reserve(ctx, max_messages): scratch for checks of up to max_messages datagrams; a call that
+ *   needs more allocates it, except on a capturing stream (WG_EINVAL: reserve first). */
+#define WG_B2S_OK 0u
+#define WG_B2S_BADDESC 1u
+#define WG_HS_OK 0u
+#define WG_HS_BADLEN 1u  /* index or datagram out of bounds, or not the exact size of its type */
+#define WG_HS_BADTYPE 2u /* the type byte is neither 1 nor 2 */
+#define WG_HS_BADMAC1 3u
+#define WG_HS_BADMAC2 4u /* mac2 is not all zero */
+#define WG_HS_INIT_SIZE 148u
+#define WG_HS_RESP_SIZE 92u
+typedef struct wg_b2s_desc { /* 32 bytes, 16-byte aligned */
+  uint64_t in_off, out_off, key_off;
+  uint32_t len;
+  uint8_t outlen, keylen, _pad[2];
+} wg_b2s_desc;
+typedef struct wg_hs_record { /* 160 bytes */
+  uint32_t index; /* batch index of the datagram */
+  uint32_t len;   /* 148 or 92 */
+  uint8_t msg[148];
+  uint32_t _pad;
+} wg_hs_record;
+typedef struct wg_hs_summary {
+  uint32_t n_valid, n_init, n_resp, n_rejected;
+} wg_hs_summary;
+typedef struct wg_hs_batch {
+  const uint8_t* wire;     /* UDP ring (device) */
+  uint64_t wire_size;
+  const uint64_t* pkt_off; /* device, n entries */
+  const uint32_t* pkt_len; /* device, n entries */
+  const uint32_t* list;    /* device, batch indices (the plan's host_list), or NULL: all n datagrams */
+  const uint32_t* n_list;  /* device, the list's length (&wg_rx_summary.n_host); NULL with list = NULL */
+  uint32_t* hs_status;     /* device, n entries, WG_HS_*, indexed by list position */
+  wg_hs_record* records;   /* device, 16-byte aligned, n entries */
+  wg_hs_summary* summary;  /* device, 16 bytes */
+  uint32_t n;
+  uint32_t _reserved;
+} wg_hs_batch;
+int wg_blake2s_batch(wg_ctx* ctx, const wg_b2s_desc* desc_dev, uint32_t n, const uint8_t* in_dev, uint64_t in_size,
+                     uint8_t* out_dev, uint64_t out_size, uint32_t* status_dev, void* stream);
+int wg_hs_key_set(wg_ctx* ctx, const uint8_t* static_public /* 32 bytes */);
+int wg_hs_reserve(wg_ctx* ctx, uint32_t max_messages);
+int wg_hs_check(wg_ctx* ctx, const wg_hs_batch* batch, void* stream);
+
 int wg_seal1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* pt, uint32_t len, uint8_t* out);
 int wg_open1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* in, uint32_t len, uint8_t* pt);
 int wg_pp_config(wg_ctx* ctx, uint32_t waves, uint32_t idle_us);

@@ -42,6 +42,15 @@ WG_TX_BROADCAST = 0
 WG_TX_ROUTE = 1
 WG_RX_PT_AFTER = 0
 WG_RX_PT_PACKED = 1
+WG_B2S_OK = 0
+WG_B2S_BADDESC = 1
+WG_HS_OK = 0
+WG_HS_BADLEN = 1
+WG_HS_BADTYPE = 2
+WG_HS_BADMAC1 = 3
+WG_HS_BADMAC2 = 4
+WG_HS_INIT_SIZE = 148
+WG_HS_RESP_SIZE = 92
 WG_MAX_FILTERS = 65536
 WG_NO_FILTER = 0xFFFFFFFF
 WG_LEN_INVALID = 0xFFFFFFFF
@@ -131,6 +140,33 @@ class WgRxDeliverBatch(ctypes.Structure):
                 ("delivered", ctypes.c_void_p), ("n", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
 
 
+class WgB2sDesc(ctypes.Structure):
+    """wg_b2s_desc: one message of wg_blake2s_batch."""
+    _fields_ = [("in_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64), ("key_off", ctypes.c_uint64),
+                ("len", ctypes.c_uint32), ("outlen", ctypes.c_uint8), ("keylen", ctypes.c_uint8),
+                ("_pad", ctypes.c_uint8 * 2)]
+
+
+class WgHsRecord(ctypes.Structure):
+    """wg_hs_record: one accepted handshake message of wg_hs_check."""
+    _fields_ = [("index", ctypes.c_uint32), ("len", ctypes.c_uint32), ("msg", ctypes.c_uint8 * 148),
+                ("_pad", ctypes.c_uint32)]
+
+
+class WgHsSummary(ctypes.Structure):
+    """wg_hs_summary: totals of one wg_hs_check call."""
+    _fields_ = [("n_valid", ctypes.c_uint32), ("n_init", ctypes.c_uint32), ("n_resp", ctypes.c_uint32),
+                ("n_rejected", ctypes.c_uint32)]
+
+
+class WgHsBatch(ctypes.Structure):
+    """wg_hs_batch: one wg_hs_check call (device pointers)."""
+    _fields_ = [("wire", ctypes.c_void_p), ("wire_size", ctypes.c_uint64), ("pkt_off", ctypes.c_void_p),
+                ("pkt_len", ctypes.c_void_p), ("list", ctypes.c_void_p), ("n_list", ctypes.c_void_p),
+                ("hs_status", ctypes.c_void_p), ("records", ctypes.c_void_p), ("summary", ctypes.c_void_p),
+                ("n", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
+
+
 class WgCompletion(ctypes.Structure):
     """wg_completion: one reaped packet of a wg_queue."""
     _fields_ = [("user", ctypes.c_uint64), ("counter", ctypes.c_uint64), ("data", ctypes.c_void_p),
@@ -148,6 +184,8 @@ assert ctypes.sizeof(WgBatch) == 64 and ctypes.sizeof(WgCompletion) == 48 and ct
 assert ctypes.sizeof(WgTxBatch) == 88
 assert ctypes.sizeof(WgRxBatch) == 96 and ctypes.sizeof(WgRxDeliverBatch) == 64
 assert ctypes.sizeof(WgRxSummary) == 16 and ctypes.sizeof(WgRxItem) == 16 and ctypes.sizeof(WgRxDelivered) == 16
+assert ctypes.sizeof(WgB2sDesc) == 32 and ctypes.sizeof(WgHsRecord) == 160 and ctypes.sizeof(WgHsSummary) == 16
+assert ctypes.sizeof(WgHsBatch) == 80
 assert ctypes.sizeof(WgPkt) == 32 and ctypes.sizeof(WgAeadDesc) == 64 and ctypes.sizeof(WgPrefix) == 18
 
 # (name, restype, argtypes) for every symbol include/wgaead.h declares
@@ -189,6 +227,10 @@ SIGNATURES = [
     ("wg_rx_reserve", _I, [_VP, _U32]),
     ("wg_rx_plan", _I, [_VP, ctypes.POINTER(WgRxBatch), _VP]),
     ("wg_rx_deliver", _I, [_VP, ctypes.POINTER(WgRxDeliverBatch), _VP]),
+    ("wg_blake2s_batch", _I, [_VP, _VP, _U32, _VP, _U64, _VP, _U64, _VP, _VP]),
+    ("wg_hs_key_set", _I, [_VP, _VP]),
+    ("wg_hs_reserve", _I, [_VP, _U32]),
+    ("wg_hs_check", _I, [_VP, ctypes.POINTER(WgHsBatch), _VP]),
     ("wg_seal1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_open1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_pp_config", _I, [_VP, _U32, _U32]),

@@ -95,6 +95,7 @@ int rx_tables(wg_ctx* c, const wgt::RxTables** out);  // wg_rx.hip
 struct RxState;  // wg_rx.hip
 struct TxState;  // wg_tx.hip
 struct RxPlanState;  // wg_rxplan.hip
+struct HsState;  // wg_hs.hip
 
 }  // namespace
 
@@ -171,6 +172,7 @@ struct wg_ctx {
   RxState* rx = nullptr;  // receive-side checks (wg_rx.hip)
   TxState* tx = nullptr;  // transmit-side planning: send counters, peers, routes (wg_tx.hip)
   RxPlanState* rxp = nullptr;  // receive-side planning: session table, scratch (wg_rxplan.hip)
+  HsState* hs = nullptr;  // handshake admission: mac1 key, scratch (wg_hs.hip)
   // timing
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -799,6 +801,7 @@ int launch_after_seal(wg_ctx* c, const wg_batch* sb, const wg_batch* ob, hipStre
 #include "wg_rx.hip"
 #include "wg_tx.hip"
 #include "wg_rxplan.hip"
+#include "wg_hs.hip"
 
 extern "C" {
 
@@ -918,6 +921,7 @@ int wg_ctx_destroy(wg_ctx* c) {
   rx_free(c);
   tx_free(c);
   rxp_free(c);
+  hs_free(c);
   if (c->keys) {
     (void)hipDeviceSynchronize();  // no launch of this context may still read the table
     (void)hipMemsetAsync(c->keys, 0, (size_t)c->key_slots * 32, c->stream);  // SymmetricKeypair.clean zeroes keys

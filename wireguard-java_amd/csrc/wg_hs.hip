@@ -1,0 +1,470 @@
+// wg_hs.hip — batched BLAKE2s and the handshake admission check, on the device (included by wg_capi.hip).
+//
+// The reference runs mac1, WireGuard's first admission test, on every incoming initiation and response
+// before any Noise work (IncomingInitiation.java:24-40, IncomingResponse.java:20-36): the keyed hash
+// BLAKE2s-128(key = BLAKE2s-256("mac1----" || static public key), message without its two MACs)
+// (InitiationPacket.calculateMac1, InitiationPacket.java:110-120; ResponsePacket.java:107-117) must equal
+// the message's mac1 field, and mac2 must be all zero (IncomingInitiation.java:38-40: no cookies).
+// wg_rx_plan lists the type-1 / type-2 datagrams of a UDP ring; wg_hs_check runs that test over the list
+// where the ring lies and hands the host the accepted messages as compact records, so the host never
+// fetches the ring and never hashes a message that was not meant for this device.
+//
+// BLAKE2s (RFC 7693), sequential mode, fanout 1, depth 1: parameter word outlen | keylen << 8 |
+// 0x01010000 (Blake2s.java:94); a key is the first block, zero-padded (Blake2s.java:95-98). One message
+// per lane: h[8], m[16] and v[16] in registers, the ten rounds unrolled with the message schedule as
+// compile-time constants, so nothing is indexed dynamically and the kernels use no scratch. The right
+// rotations by 16 and 8 are one v_perm_b32 each, those by 12 and 7 one v_alignbit_b32 each (the ChaCha20
+// rotates of wg_device.h, turned the other way). Lanes of a wave hash messages of different lengths: the
+// wave walks as many blocks as its longest message has.
+//
+// Message bytes are fetched as whole aligned 32-bit words (those that hold at least one byte of the
+// range, never another) and shifted into place, so a message at any alignment costs 17 loads per block
+// instead of 64; the bytes behind the range are masked to zero.
+//
+// Ranks. records[0 .. n_valid) is the stable compaction of the accepted messages; it takes the three
+// launches of wg_rxplan.hip's ranks (check, scan, emit), with k_rx_scan called as it is: the check
+// launch leaves one 16-B record {valid, initiations, responses, rejected} per range of 256 list
+// positions, the scan turns them into exclusive prefixes and writes their totals as the summary, the
+// emit launch places. The list's length is read on the device (it is the plan's n_host, written earlier
+// on the same stream): the grid is sized from n, and a workgroup past the list writes a zero record and
+// exits. Every scratch word is written by the first launch of a call before a later one reads it and
+// nothing about a call lives on the host, so a captured plan + check replays. The mac1 key sits at a
+// fixed device address (the TxRouteHdr pattern of wg_tx.hip): wg_hs_key_set between replays needs no
+// re-capture.
+#pragma once
+
+namespace {
+
+struct HsState {
+  DevBuf d_key;    // the mac1 key, 32 B (fixed address)
+  DevBuf d_stage;  // wg_hs_key_set: descriptor, "mac1----" || public key, status
+  DevBuf d_part;   // per range of 256 list positions: {valid, init, resp, rejected}, then their exclusive prefixes
+  bool has_key = false;
+  hipEvent_t ev = nullptr;  // last use of the scratch, and its stream
+  hipStream_t ev_stream = (hipStream_t)-1;
+};
+
+// The handshake state, allocated at the first wg_hs_* call. Caller holds c->mu.
+int hs_get(wg_ctx* c, HsState** out) {
+  if (!c->hs) {
+    auto t = std::make_unique<HsState>();
+    int rc;
+    if ((rc = t->d_key.ensure(32)) != WG_OK || (rc = t->d_stage.ensure(256)) != WG_OK) {
+      for (DevBuf* b : {&t->d_key, &t->d_stage}) b->release();
+      return rc;
+    }
+    hipError_t e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_key.p, 0, 32, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+      for (DevBuf* b : {&t->d_key, &t->d_stage}) b->release();
+      if (t->ev) (void)hipEventDestroy(t->ev);
+      return fail(WG_EDEVICE, "handshake state: %s", hipGetErrorString(e));
+    }
+    c->hs = t.release();
+  }
+  *out = c->hs;
+  return WG_OK;
+}
+
+void hs_free(wg_ctx* c) {
+  if (!c->hs) return;
+  HsState* t = c->hs;
+  if (t->d_key.p) {  // the key is wiped, like the key table
+    (void)hipDeviceSynchronize();
+    (void)hipMemsetAsync(t->d_key.p, 0, 32, c->stream);
+    (void)hipStreamSynchronize(c->stream);
+  }
+  for (DevBuf* b : {&t->d_key, &t->d_stage, &t->d_part}) b->release();
+  if (t->ev) (void)hipEventDestroy(t->ev);
+  delete t;
+  c->hs = nullptr;
+}
+
+bool hs_scratch_fits(const HsState* t, uint32_t n) { return (size_t)std::max(rxp_blocks(n), 1u) * 16 <= t->d_part.cap; }
+// scratch for checks of up to n messages; never on a capturing stream (the caller checks)
+int hs_scratch(HsState* t, uint32_t n) {
+  if (hs_scratch_fits(t, n)) return WG_OK;
+  HIPTRY(hipDeviceSynchronize());  // the scratch is reallocated under earlier calls
+  return t->d_part.ensure((size_t)std::max(rxp_blocks(n), 1u) * 16);
+}
+
+}  // namespace
+
+// ---- device -------------------------------------------------------------------------------
+namespace wghs {
+
+struct B2sParams {
+  const wg_b2s_desc* desc;
+  const uint8_t* in;
+  uint64_t in_size;
+  uint8_t* out;
+  uint64_t out_size;
+  uint32_t* status;
+  uint32_t n;
+};
+
+struct HsParams {
+  const uint8_t* wire;
+  uint64_t wire_size;
+  const uint64_t* pkt_off;
+  const uint32_t* pkt_len;
+  const uint32_t* list;
+  const uint32_t* n_list;
+  uint32_t* hs_status;
+  wg_hs_record* records;
+  const uint8_t* key;
+  uint4* part;
+  uint32_t n;
+};
+
+__device__ __forceinline__ uint32_t rotr16(uint32_t x) { return wgd::rotl16(x); }
+__device__ __forceinline__ uint32_t rotr12(uint32_t x) { return wgd::rotl(x, 20); }
+__device__ __forceinline__ uint32_t rotr8(uint32_t x) { return __builtin_amdgcn_perm(x, x, 0x00030201u); }
+__device__ __forceinline__ uint32_t rotr7(uint32_t x) { return wgd::rotl(x, 25); }
+
+#define WG_B2S_G(a, b, c, d, x, y)               \
+  v[a] += v[b] + (x); v[d] = rotr16(v[d] ^ v[a]); \
+  v[c] += v[d];       v[b] = rotr12(v[b] ^ v[c]); \
+  v[a] += v[b] + (y); v[d] = rotr8(v[d] ^ v[a]);  \
+  v[c] += v[d];       v[b] = rotr7(v[b] ^ v[c]);
+// one round: four columns, four diagonals; s0..s15 = the round's row of the sigma permutation
+#define WG_B2S_ROUND(s0, s1, s2, s3, s4, s5, s6, s7, s8, s9, s10, s11, s12, s13, s14, s15) \
+  WG_B2S_G(0, 4, 8, 12, m[s0], m[s1])                                                      \
+  WG_B2S_G(1, 5, 9, 13, m[s2], m[s3])                                                      \
+  WG_B2S_G(2, 6, 10, 14, m[s4], m[s5])                                                     \
+  WG_B2S_G(3, 7, 11, 15, m[s6], m[s7])                                                     \
+  WG_B2S_G(0, 5, 10, 15, m[s8], m[s9])                                                     \
+  WG_B2S_G(1, 6, 11, 12, m[s10], m[s11])                                                   \
+  WG_B2S_G(2, 7, 8, 13, m[s12], m[s13])                                                    \
+  WG_B2S_G(3, 4, 9, 14, m[s14], m[s15])
+
+// RFC 7693 3.2: h = F(h, m, t, last)
+__device__ __forceinline__ void b2s_compress(uint32_t h[8], const uint32_t m[16], uint64_t t, bool last) {
+  uint32_t v[16];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = h[k];
+  v[8] = 0x6A09E667u;
+  v[9] = 0xBB67AE85u;
+  v[10] = 0x3C6EF372u;
+  v[11] = 0xA54FF53Au;
+  v[12] = 0x510E527Fu ^ (uint32_t)t;
+  v[13] = 0x9B05688Cu ^ (uint32_t)(t >> 32);
+  v[14] = 0x1F83D9ABu ^ (last ? 0xFFFFFFFFu : 0u);
+  v[15] = 0x5BE0CD19u;
+  WG_B2S_ROUND(0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
+  WG_B2S_ROUND(14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3)
+  WG_B2S_ROUND(11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4)
+  WG_B2S_ROUND(7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8)
+  WG_B2S_ROUND(9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13)
+  WG_B2S_ROUND(2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9)
+  WG_B2S_ROUND(12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11)
+  WG_B2S_ROUND(13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10)
+  WG_B2S_ROUND(6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5)
+  WG_B2S_ROUND(10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0)
+#pragma unroll
+  for (int k = 0; k < 8; ++k) h[k] ^= v[k] ^ v[k + 8];
+}
+
+// m = the `avail` (0..64) bytes at p as little-endian words, zero behind them. Reads the aligned words
+// that hold at least one of those bytes: an index past the last such word is clamped to it, so no load
+// is conditional and none leaves the range's own words.
+__device__ __forceinline__ void b2s_load(const uint8_t* p, uint32_t avail, uint32_t m[16]) {
+  if (avail == 0) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) m[k] = 0u;
+    return;
+  }
+  const uint32_t mis = (uint32_t)((uintptr_t)p & 3u);
+  const uint32_t* base = (const uint32_t*)(p - mis);
+  const uint32_t jlast = (mis + avail - 1u) >> 2;  // <= 16
+  uint32_t w[17];
+#pragma unroll
+  for (uint32_t j = 0; j < 17; ++j) w[j] = base[j < jlast ? j : jlast];
+  const uint32_t sh = 8u * mis;
+#pragma unroll
+  for (uint32_t k = 0; k < 16; ++k) {
+    const uint32_t x = __builtin_amdgcn_alignbit(w[k + 1], w[k], sh);
+    const uint32_t vb = avail > 4u * k ? avail - 4u * k : 0u;
+    m[k] = x & (vb >= 4u ? 0xFFFFFFFFu : (1u << (8u * vb)) - 1u);
+  }
+}
+
+// h = the BLAKE2s state after msg[0 .. len) under key[0 .. keylen) for a digest of outlen bytes: the
+// digest is the first outlen bytes of h, little-endian.
+__device__ __forceinline__ void b2s_hash(const uint8_t* msg, uint32_t len, const uint8_t* key, uint32_t keylen,
+                                         uint32_t outlen, uint32_t h[8]) {
+  h[0] = 0x6A09E667u ^ (outlen | (keylen << 8) | 0x01010000u);
+  h[1] = 0xBB67AE85u;
+  h[2] = 0x3C6EF372u;
+  h[3] = 0xA54FF53Au;
+  h[4] = 0x510E527Fu;
+  h[5] = 0x9B05688Cu;
+  h[6] = 0x1F83D9ABu;
+  h[7] = 0x5BE0CD19u;
+  const uint32_t kb = keylen ? 1u : 0u;  // the key block; it is the last block of a keyed empty message
+  const uint32_t mb = len ? (len >> 6) + ((len & 63u) ? 1u : 0u) : 1u - kb;
+  const uint32_t nb = kb + mb;
+  uint64_t t = 0;
+  for (uint32_t b = 0; b < nb; ++b) {
+    const bool isk = b < kb;
+    const uint64_t off = 64ull * (b - kb);
+    const uint32_t left = len - (uint32_t)off;
+    const uint8_t* p = isk ? key : msg + off;
+    const uint32_t avail = isk ? keylen : (left < 64u ? left : 64u);
+    t += isk ? 64u : avail;
+    uint32_t m[16];
+    b2s_load(p, avail, m);
+    b2s_compress(h, m, t, b + 1u == nb);
+  }
+}
+
+__global__ void __launch_bounds__(256) k_b2s(B2sParams P) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= P.n) return;
+  const uint4* d = (const uint4*)(P.desc + i);
+  const uint4 a = d[0], b = d[1];
+  const uint64_t in_off = wgrp::u64_of(a.x, a.y), out_off = wgrp::u64_of(a.z, a.w), key_off = wgrp::u64_of(b.x, b.y);
+  const uint32_t len = b.z, outlen = b.w & 0xFFu, keylen = (b.w >> 8) & 0xFFu;
+  // (off <= size && len <= size - off: no sum that could wrap)
+  const bool ok = outlen >= 1u && outlen <= 32u && keylen <= 32u && in_off <= P.in_size &&
+                  (uint64_t)len <= P.in_size - in_off && key_off <= P.in_size &&
+                  (uint64_t)keylen <= P.in_size - key_off && out_off <= P.out_size &&
+                  (uint64_t)outlen <= P.out_size - out_off;
+  if (!ok) {
+    P.status[i] = WG_B2S_BADDESC;
+    return;
+  }
+  uint32_t h[8];
+  b2s_hash(P.in + in_off, len, P.in + key_off, keylen, outlen, h);
+  uint8_t* o = P.out + out_off;
+#pragma unroll
+  for (uint32_t k = 0; k < 8; ++k) {
+    if (4u * k + 4u <= outlen) {
+      wgt::store_u32_any(o + 4u * k, h[k]);
+    } else {  // the digest's last word, partly written (or not at all)
+#pragma unroll
+      for (uint32_t j = 0; j < 3; ++j)
+        if (4u * k + j < outlen) o[4u * k + j] = (uint8_t)(h[k] >> (8u * j));
+    }
+  }
+  P.status[i] = WG_B2S_OK;
+}
+
+// list position k -> batch index, and how long the list is (read on the device)
+__device__ __forceinline__ uint32_t hs_list_len(const HsParams& P) {
+  if (!P.list) return P.n;
+  const uint32_t nl = *P.n_list;
+  return nl < P.n ? nl : P.n;
+}
+
+// steps 1-6 of wg_hs_check for one list position per thread; the range's counts
+__global__ void __launch_bounds__(256) k_hs_check(HsParams P) {
+  __shared__ uint32_t s_cnt[4][4];
+  const uint32_t nl = hs_list_len(P);
+  if (blockIdx.x * kRxRange >= nl) {  // past the list (workgroup-uniform): a zero record for the scan
+    if (threadIdx.x == 0) P.part[blockIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+    return;
+  }
+  const uint32_t k = blockIdx.x * kRxRange + threadIdx.x;
+  const bool in = k < nl;
+  uint32_t st = WG_HS_BADLEN, t = 0;
+  if (in) {
+    const uint32_t i = P.list ? P.list[k] : k;
+    bool go = false;
+    const uint8_t* msg = P.wire;
+    uint32_t L = 0;
+    if (i < P.n) {
+      const uint64_t o = P.pkt_off[i];
+      const uint32_t wl = P.pkt_len[i];
+      if (wl != 0 && o <= P.wire_size && (uint64_t)wl <= P.wire_size - o) {
+        msg = P.wire + o;
+        t = msg[0];
+        if (t != 1u && t != 2u) {
+          st = WG_HS_BADTYPE;
+        } else {
+          L = t == 1u ? 148u : 92u;
+          go = wl == L;
+        }
+      }
+    }
+    if (go) {
+      uint32_t h[8];
+      b2s_hash(msg, L - 32u, P.key, 32u, 16u, h);
+      uint32_t diff = 0, mac2 = 0;  // all 16 bytes of each, no early exit
+#pragma unroll
+      for (uint32_t j = 0; j < 4; ++j) {
+        diff |= wgt::load_u32_any(msg + L - 32u + 4u * j) ^ h[j];
+        mac2 |= wgt::load_u32_any(msg + L - 16u + 4u * j);
+      }
+      st = diff ? WG_HS_BADMAC1 : mac2 ? WG_HS_BADMAC2 : WG_HS_OK;
+    }
+    P.hs_status[k] = st;
+  }
+  const bool ok = in && st == WG_HS_OK;
+  uint32_t r, n_valid, n_init, n_resp, n_rej;
+  wgrp::block_rank(ok, s_cnt[0], r, n_valid);
+  wgrp::block_rank(ok && t == 1u, s_cnt[1], r, n_init);
+  wgrp::block_rank(ok && t == 2u, s_cnt[2], r, n_resp);
+  wgrp::block_rank(in && !ok, s_cnt[3], r, n_rej);
+  if (threadIdx.x == 0) P.part[blockIdx.x] = make_uint4(n_valid, n_init, n_resp, n_rej);
+}
+
+// records[prefix of the range + rank in the range] = the accepted message of this list position
+__global__ void __launch_bounds__(256) k_hs_emit(HsParams P) {
+  __shared__ uint32_t s_cnt[4];
+  const uint32_t nl = hs_list_len(P);
+  if (blockIdx.x * kRxRange >= nl) return;  // (workgroup-uniform)
+  const uint32_t k = blockIdx.x * kRxRange + threadIdx.x;
+  const bool ok = k < nl && P.hs_status[k] == WG_HS_OK;
+  const uint4 pre = P.part[blockIdx.x];
+  uint32_t r, total;
+  wgrp::block_rank(ok, s_cnt, r, total);
+  if (!ok) return;
+  const uint32_t i = P.list ? P.list[k] : k;
+  const uint8_t* msg = P.wire + P.pkt_off[i];
+  const uint32_t L = msg[0] == 1u ? 148u : 92u;
+  uint4* rec = (uint4*)(P.records + (pre.x + r));
+#pragma unroll
+  for (uint32_t g = 0; g < 10; ++g) {  // 160 B: index, len, 37 message words (zero behind a response), _pad
+    uint32_t w[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+      const uint32_t q = 4u * g + j;
+      if (q == 0) w[j] = i;
+      else if (q == 1) w[j] = L;
+      else if (q == 39) w[j] = 0u;
+      else w[j] = 4u * (q - 2u) < L ? wgt::load_u32_any(msg + 4u * (q - 2u)) : 0u;
+    }
+    rec[g] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}
+
+}  // namespace wghs
+
+// ---- C ABI --------------------------------------------------------------------------------
+namespace {
+
+int b2s_launch(const wg_b2s_desc* desc, uint32_t n, const uint8_t* in, uint64_t in_size, uint8_t* out, uint64_t out_size,
+               uint32_t* status, hipStream_t s) {
+  wghs::B2sParams P{};
+  P.desc = desc;
+  P.in = in;
+  P.in_size = in_size;
+  P.out = out;
+  P.out_size = out_size;
+  P.status = status;
+  P.n = n;
+  hipLaunchKernelGGL(wghs::k_b2s, dim3(rxp_blocks(n)), dim3(256), 0, s, P);
+  const hipError_t le = hipGetLastError();
+  if (le != hipSuccess) return fail(WG_EDEVICE, "k_b2s launch: %s", hipGetErrorString(le));
+  return WG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wg_blake2s_batch(wg_ctx* c, const wg_b2s_desc* desc, uint32_t n, const uint8_t* in, uint64_t in_size, uint8_t* out,
+                     uint64_t out_size, uint32_t* status, void* stream) {
+  if (!c) return fail(WG_EINVAL, "NULL context");
+  if (n == 0) return WG_OK;
+  if (!desc || (((uintptr_t)desc) & 15u)) return fail(WG_EINVAL, "descriptor array must be non-NULL and 16-byte aligned");
+  if (!in || !out || !status || (((uintptr_t)status) & 3u))
+    return fail(WG_EINVAL, "NULL input, output or status array (status: 4-byte aligned)");
+  if (open_overlaps(in, in_size, out, out_size)) return fail(WG_EINVAL, "the output buffer must not overlap the input buffer");
+  DeviceGuard g(c->device);
+  return b2s_launch(desc, n, in, in_size, out, out_size, status, pick_stream(c, stream));
+}
+
+int wg_hs_key_set(wg_ctx* c, const uint8_t* static_public) {
+  if (!c || !static_public) return fail(WG_EINVAL, "NULL argument");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  HsState* t;
+  int rc;
+  if ((rc = hs_get(c, &t)) != WG_OK) return rc;
+  // stage: [0, 32) the descriptor, [32, 72) "mac1----" || public key (InitiationPacket.java:111-115), [96, 100) status
+  uint8_t host[128] = {0};
+  wg_b2s_desc d{};
+  d.in_off = 32;
+  d.len = 40;
+  d.outlen = 32;
+  memcpy(host, &d, sizeof d);
+  memcpy(host + 32, "mac1----", 8);
+  memcpy(host + 40, static_public, 32);
+  HIPTRY(hipDeviceSynchronize());  // no check queued earlier (on any stream) may still read the old key
+  uint8_t* st = (uint8_t*)t->d_stage.p;
+  HIPTRY(hipMemcpyAsync(st, host, sizeof host, hipMemcpyHostToDevice, c->stream));
+  if ((rc = b2s_launch((const wg_b2s_desc*)st, 1, st, 128, (uint8_t*)t->d_key.p, 32, (uint32_t*)(st + 96), c->stream)) != WG_OK)
+    return rc;
+  HIPTRY(hipStreamSynchronize(c->stream));
+  t->has_key = true;
+  return WG_OK;
+}
+
+int wg_hs_reserve(wg_ctx* c, uint32_t max_messages) {
+  if (!c) return fail(WG_EINVAL, "NULL context");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  HsState* t;
+  int rc;
+  if ((rc = hs_get(c, &t)) != WG_OK) return rc;
+  return hs_scratch(t, max_messages);
+}
+
+int wg_hs_check(wg_ctx* c, const wg_hs_batch* b, void* stream) {
+  if (!c || !b) return fail(WG_EINVAL, "NULL argument");
+  if (b->_reserved) return fail(WG_EINVAL, "wg_hs_batch._reserved must be 0");
+  if (!b->summary || (((uintptr_t)b->summary) & 7u)) return fail(WG_EINVAL, "summary must be non-NULL and 8-byte aligned");
+  if ((b->list == nullptr) != (b->n_list == nullptr))
+    return fail(WG_EINVAL, "list and n_list go together: both NULL (every datagram) or both set");
+  if ((((uintptr_t)b->list) & 3u) || (((uintptr_t)b->n_list) & 3u)) return fail(WG_EINVAL, "list and n_list must be 4-byte aligned");
+  hipStream_t s = pick_stream(c, stream);
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  if (!c->hs || !c->hs->has_key) return fail(WG_ENOKEY, "wg_hs_check before any wg_hs_key_set");
+  HsState* t = c->hs;
+  const bool capturing = tx_capturing(s);
+  const uint32_t n = b->n;
+  if (n == 0) {
+    HIPTRY(hipMemsetAsync(b->summary, 0, sizeof(wg_hs_summary), s));
+    return WG_OK;
+  }
+  if (!b->wire || !b->pkt_off || !b->pkt_len) return fail(WG_EINVAL, "NULL wire ring or packet table");
+  if (!b->hs_status || (((uintptr_t)b->hs_status) & 3u) || !b->records || (((uintptr_t)b->records) & 15u))
+    return fail(WG_EINVAL, "status / record output must be non-NULL and aligned (4 / 16 bytes)");
+  int rc;
+  if (capturing) {
+    if (!hs_scratch_fits(t, n))
+      return fail(WG_EINVAL, "handshake check of %u datagrams on a capturing stream needs more scratch: call wg_hs_reserve(%u) first", n, n);
+  } else {
+    if ((rc = hs_scratch(t, n)) != WG_OK) return rc;
+    if (t->ev_stream != s && t->ev_stream != (hipStream_t)-1) HIPTRY(hipStreamWaitEvent(s, t->ev, 0));
+  }
+  wghs::HsParams P{};
+  P.wire = b->wire;
+  P.wire_size = b->wire_size;
+  P.pkt_off = b->pkt_off;
+  P.pkt_len = b->pkt_len;
+  P.list = b->list;
+  P.n_list = b->n_list;
+  P.hs_status = b->hs_status;
+  P.records = b->records;
+  P.key = (const uint8_t*)t->d_key.p;
+  P.part = (uint4*)t->d_part.p;
+  P.n = n;
+  const uint32_t nb = rxp_blocks(n);
+  hipLaunchKernelGGL(wghs::k_hs_check, dim3(nb), dim3(256), 0, s, P);
+  hipLaunchKernelGGL(wgrp::k_rx_scan, dim3(1), dim3(256), 0, s, P.part, nb, (uint2*)b->summary);
+  hipLaunchKernelGGL(wghs::k_hs_emit, dim3(nb), dim3(256), 0, s, P);
+  const hipError_t le = hipGetLastError();
+  if (le != hipSuccess) return fail(WG_EDEVICE, "handshake check kernels: %s", hipGetErrorString(le));
+  if (!capturing) {
+    HIPTRY(hipEventRecord(t->ev, s));
+    t->ev_stream = s;
+  }
+  return WG_OK;
+}
+
+}  // extern "C"

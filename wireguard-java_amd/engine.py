@@ -36,6 +36,20 @@ WG_AEAD_DTYPE = np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("aad_off", "<u
                           ("_reserved", "<u4", (3,))])
 
 
+WG_B2S_DTYPE = np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("key_off", "<u8"), ("len", "<u4"), ("outlen", "u1"),
+                         ("keylen", "u1"), ("_pad", "u1", (2,))])
+WG_HS_RECORD_DTYPE = np.dtype([("index", "<u4"), ("len", "<u4"), ("msg", "u1", (148,)), ("_pad", "<u4")])
+
+
+def pack_b2s_desc(in_off, out_off, key_off, length, outlen, keylen) -> np.ndarray:
+    """Build a wg_b2s_desc array (numpy structured) from per-message columns."""
+    n = len(np.atleast_1d(in_off))
+    d = np.zeros(n, WG_B2S_DTYPE)
+    d["in_off"], d["out_off"], d["key_off"] = in_off, out_off, key_off
+    d["len"], d["outlen"], d["keylen"] = length, outlen, keylen
+    return d
+
+
 def desc_as_int64(d: np.ndarray) -> np.ndarray:
     """wg_pkt array viewed as int64 [n, 4] (for torch.from_numpy)."""
     d = np.ascontiguousarray(d)
@@ -327,6 +341,70 @@ class Engine:
             self.rx_check(desc_out, out, open_status, L.WG_RX_REPLAY, stream=st)
         self.rx_deliver(desc_out, rx_status, open_status, final_status, items, delivered, index_out=index_out,
                         stream=st)
+
+    # ---- handshake admission (wg_blake2s_batch / wg_hs_check) -------------------------------
+    def blake2s(self, desc, inp, out, status, stream: int | None = None) -> None:
+        """wg_blake2s_batch over torch tensors: desc int64 [n, 4] (wg_b2s_desc records, pack_b2s_desc),
+        inp / out uint8 (device, not overlapping), status int32 [n] (WG_B2S_*). Keys are read from inp."""
+        n = desc.shape[0]
+        L.check(self._lib.wg_blake2s_batch(self.ctx, desc.data_ptr(), n, inp.data_ptr(), inp.numel(), out.data_ptr(),
+                                           out.numel(), status.data_ptr(),
+                                           stream if stream is not None else _torch_stream()))
+
+    def blake2s_host(self, messages) -> list[bytes]:
+        """BLAKE2s of host byte strings through one wg_blake2s_batch call: messages = [(data, key,
+        outlen)]; returns the digests. For the noise mirror and tests; a data path keeps its bytes on
+        the device and calls blake2s()."""
+        import torch
+        if not messages:
+            return []
+        dev = torch.device("cuda", self.device)
+        buf, rows, out_off = bytearray(), [], 0
+        for data, key, outlen in messages:
+            if not 1 <= outlen <= 32 or len(key) > 32:
+                raise L.WgError(L.WG_EINVAL, "digest length must be in [1, 32], key length at most 32")
+            rows.append((len(buf), out_off, len(buf) + len(data), len(data), outlen, len(key)))
+            buf += bytes(data) + bytes(key)
+            out_off += 32
+        d = pack_b2s_desc(*(np.array(c, np.uint64) for c in zip(*rows)))
+        d_desc = torch.from_numpy(desc_as_int64(d)).to(dev)
+        d_in = torch.from_numpy(np.frombuffer(bytes(buf) + b"\0", np.uint8).copy()).to(dev)
+        d_out = torch.zeros(out_off, dtype=torch.uint8, device=dev)
+        d_st = torch.zeros(len(rows), dtype=torch.int32, device=dev)
+        st = _torch_stream()
+        self.blake2s(d_desc, d_in, d_out, d_st, stream=st)
+        self.sync(st)
+        if int(d_st.abs().sum().item()):
+            raise L.WgError(L.WG_EINVAL, "wg_blake2s_batch refused a descriptor")
+        out = d_out.cpu().numpy().tobytes()
+        return [out[32 * k:32 * k + m[2]] for k, m in enumerate(messages)]
+
+    def hs_key_set(self, static_public) -> None:
+        """wg_hs_key_set: the mac1 key of the local static public key (32 bytes), derived on the device."""
+        pub = np.frombuffer(bytes(static_public), np.uint8).copy()
+        if pub.size != 32:
+            raise L.WgError(L.WG_EINVAL, f"static public key of {pub.size} bytes")
+        L.check(self._lib.wg_hs_key_set(self.ctx, pub.ctypes.data))
+
+    def hs_reserve(self, max_messages: int) -> None:
+        """wg_hs_reserve: scratch for checks of up to max_messages datagrams (needed before a check is
+        captured into a graph: a capturing stream cannot allocate)."""
+        L.check(self._lib.wg_hs_reserve(self.ctx, max_messages))
+
+    def hs_check(self, wire, pkt_off, pkt_len, hs_status, records, hs_summary, host_list=None, rx_summary=None,
+                 stream: int | None = None) -> None:
+        """wg_hs_check over torch tensors: wire / pkt_off / pkt_len as rx_plan() took them, hs_status int32
+        [n], records uint8 [n, 160] (wg_hs_record, WG_HS_RECORD_DTYPE), hs_summary int32 [4] (n_valid,
+        n_init, n_resp, n_rejected). host_list and rx_summary are the tensors rx_plan() wrote: the check
+        reads the list's length (wg_rx_summary.n_host) on the device, so plan and check run back to back
+        on one stream. Without them every one of the n datagrams is checked."""
+        if (host_list is None) != (rx_summary is None):
+            raise L.WgError(L.WG_EINVAL, "host_list and rx_summary go together")
+        n_list = rx_summary.data_ptr() + L.WgRxSummary.n_host.offset if rx_summary is not None else None
+        b = L.WgHsBatch(wire.data_ptr(), wire.numel(), pkt_off.data_ptr(), pkt_len.data_ptr(),
+                        host_list.data_ptr() if host_list is not None else None, n_list, hs_status.data_ptr(),
+                        records.data_ptr(), hs_summary.data_ptr(), pkt_off.shape[0], 0)
+        L.check(self._lib.wg_hs_check(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
 
     def set_receivers(self, receivers) -> None:
         """wg_ctx_set_receivers: device tensor of receiver_index per key slot for

@@ -39,15 +39,19 @@ public final class WgAead {
 	/** wg_rx_plan outcomes beside WG_PKT_OK / WG_PKT_BADHDR / WG_PKT_TOOLONG: no session for the receiver index; a handshake message for the host. */
 	public static final int WG_PKT_NOSESSION = 10, WG_PKT_HANDSHAKE = 11;
 	public static final int WG_RX_PT_AFTER = 0, WG_RX_PT_PACKED = 1;
+	/** wg_blake2s_batch and wg_hs_check outcomes (IncomingInitiation.java:24-40, IncomingResponse.java:20-36). */
+	public static final int WG_B2S_OK = 0, WG_B2S_BADDESC = 1;
+	public static final int WG_HS_OK = 0, WG_HS_BADLEN = 1, WG_HS_BADTYPE = 2, WG_HS_BADMAC1 = 3, WG_HS_BADMAC2 = 4;
 	public static final long AEAD_DESC_SIZE = 64, PKT_DESC_SIZE = 32, BATCH_SIZE = 64, TX_BATCH_SIZE = 88,
-		RX_BATCH_SIZE = 96, RX_DELIVER_BATCH_SIZE = 64, RX_SUMMARY_SIZE = 16, RX_ITEM_SIZE = 16, RX_DELIVERED_SIZE = 16;
+		RX_BATCH_SIZE = 96, RX_DELIVER_BATCH_SIZE = 64, RX_SUMMARY_SIZE = 16, RX_ITEM_SIZE = 16, RX_DELIVERED_SIZE = 16,
+		B2S_DESC_SIZE = 32, HS_BATCH_SIZE = 80, HS_RECORD_SIZE = 160, HS_SUMMARY_SIZE = 16;
 
 	static final MethodHandle SELFTEST, CTX_CREATE, LAST_ERROR, KEYS_SET, KEYS_ZERO, SEAL1, OPEN1, AEAD_HOST,
 		SEAL_BATCH, OPEN_BATCH, SYNC, SEAL_HOST, OPEN_HOST, HOST_ALLOC, HOST_FREE, FRAME_SEAL, PARSE_OPEN,
 		FILTER_SET, SLOT_FILTERS_SET, REPLAY_ENABLE, REPLAY_RESET, RX_CHECK, DUPLEX_BATCH, QUEUE_CREATE,
 		QUEUE_DESTROY, SUBMIT_SEAL, SUBMIT_OPEN, SUBMIT_SEAL_N, SUBMIT_OPEN_N, REAP, REAP_DONE, QUEUE_SUBMIT_TIMEOUT,
 		NUMA_NODE, TX_PEERS_SET, ROUTES_SET, TX_COUNTERS_SET, TX_COUNTERS_GET, TX_RESERVE, TX_PLAN,
-		RX_SESSIONS_SET, RX_RESERVE, RX_PLAN, RX_DELIVER;
+		RX_SESSIONS_SET, RX_RESERVE, RX_PLAN, RX_DELIVER, BLAKE2S_BATCH, HS_KEY_SET, HS_RESERVE, HS_CHECK;
 
 	/** The process-wide context (one HIP device, its stream and its device key table). */
 	static final MemorySegment CTX;
@@ -116,6 +120,15 @@ public final class WgAead {
 		RX_RESERVE = down(linker, symbols, "wg_rx_reserve", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT));
 		RX_PLAN = down(linker, symbols, "wg_rx_plan", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
 		RX_DELIVER = down(linker, symbols, "wg_rx_deliver", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
+		// handshake admission: batched BLAKE2s (Blake2s.java:94), the mac1 key of the local static public key
+		// (InitiationPacket.java:110-120) and the mac1 / mac2 check of the datagrams wg_rx_plan lists
+		// (IncomingInitiation.java:24-40, IncomingResponse.java:20-36); wg_hs_check takes one wg_hs_batch
+		// struct of 80 bytes and leaves wg_hs_record entries of 160 bytes
+		BLAKE2S_BATCH = down(linker, symbols, "wg_blake2s_batch", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS,
+			JAVA_INT, ADDRESS, JAVA_LONG, ADDRESS, JAVA_LONG, ADDRESS, ADDRESS));
+		HS_KEY_SET = down(linker, symbols, "wg_hs_key_set", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS));
+		HS_RESERVE = down(linker, symbols, "wg_hs_reserve", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT));
+		HS_CHECK = down(linker, symbols, "wg_hs_check", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
 		// outgoing seal + incoming open in one launch (two wg_batch structs of 64 bytes)
 		DUPLEX_BATCH = down(linker, symbols, "wg_duplex_batch", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS,
 			ADDRESS));

@@ -2,6 +2,6 @@
 packages) whose ChaCha20-Poly1305 arithmetic runs on the MI355X through
 libwgaead. Same class and method names, argument meaning and exceptions as the
 Java sources, so the reference's own tests read the same against it."""
-from .crypto import (AEADBadTagException, BadPaddingException, ChaCha20, ChaCha20Poly1305, Crypto,  # noqa: F401
-                     IllegalStateException, Poly1305)
+from .crypto import (AEADBadTagException, BadPaddingException, Blake2s, BLAKE2s256, ChaCha20,  # noqa: F401
+                     ChaCha20Poly1305, Crypto, IllegalStateException, Poly1305, calculate_mac1)
 from .handshake import SymmetricKeypair  # noqa: F401

@@ -184,3 +184,63 @@ class ChaCha20Poly1305:
         if status[0] != L.WG_PKT_OK:
             raise AEADBadTagException(f"Invalid tag (got {list(t)})")
         _write(pt, out)
+
+
+class Blake2s:
+    """Blake2s.java: BLAKE2s (RFC 7693) with the reference's constructor, update and digest. Updates
+    are buffered and the hash is evaluated on the device at digest (wg_blake2s_batch); the instance
+    is reset afterwards, as engineDigest does (Blake2s.java:129-142)."""
+
+    BLOCK_LENGTH = 64
+
+    def __init__(self, digestLength: int, key=b""):
+        key = _bytes(key) if key is not None else None
+        if key is None:
+            raise TypeError("key is null")  # NullPointerException
+        if not len(key) <= 32:
+            raise ValueError("key's length must be at most 32")  # Blake2s.java:74-75
+        if not 1 <= digestLength <= 32:
+            raise ValueError("digestLength must be in [1, 32]")  # Blake2s.java:77-78
+        self.digestLength = digestLength
+        self._key = key
+        self._buf = bytearray()
+
+    @staticmethod
+    def algorithm() -> str:
+        return "BLAKE2s"
+
+    def reset(self) -> None:
+        self._buf = bytearray()
+
+    def update(self, input, off: int | None = None, len_: int | None = None) -> None:
+        """update(byte), update(bytes) or update(bytes, off, len) (Blake2s.java:104-127)."""
+        if isinstance(input, int):
+            self._buf.append(input & 0xFF)
+            return
+        data = _bytes(input)
+        if off is not None or len_ is not None:
+            off, len_ = off or 0, len(data) - (off or 0) if len_ is None else len_
+            if len_ < 0 or off < 0 or off + len_ > len(data):
+                raise IndexError("off or len out of bounds")  # Blake2s.java:112-114
+            data = data[off:off + len_]
+        self._buf += data
+
+    def digest(self, *data) -> bytes:
+        for d in data:
+            self.update(d)
+        out = default_engine().blake2s_host([(bytes(self._buf), self._key, self.digestLength)])[0]
+        self.reset()
+        return out
+
+
+def BLAKE2s256(*data) -> bytes:
+    """Crypto.BLAKE2s256: the unkeyed 32-byte digest of the concatenated arguments."""
+    return default_engine().blake2s_host([(b"".join(_bytes(d) for d in data), b"", 32)])[0]
+
+
+def calculate_mac1(message_without_macs, public_key) -> bytes:
+    """InitiationPacket.calculateMac1 (InitiationPacket.java:110-120; ResponsePacket.java:107-117):
+    BLAKE2s-128 of the message without its two MACs under BLAKE2s-256("mac1----" || the receiver's
+    static public key), for the outgoing side."""
+    key = BLAKE2s256(b"mac1----", _bytes(public_key))
+    return default_engine().blake2s_host([(_bytes(message_without_macs), key, 16)])[0]
