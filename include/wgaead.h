@@ -117,7 +117,8 @@ int wg_aead_selftest(int device);
  * `key_slots` 32-byte entries (zero-initialised).
  * Scheduling overrides read here from the environment, for A/B measurements only (none changes
  * a byte of output): WG_SLOT16=0|1, WG_SLOT4=0|1|2, WG_SLOT2=k, WG_MIXED_SPLIT=R, WG_UNIFORM16=k,
- * WG_PRIO=0|1, WG_LPT_ONE=0|1, WG_STREAM_WS=0|1; unset, the transport kernel plans
+ * WG_PRIO=0|1, WG_LPT_ONE=0|1, WG_STREAM_WS=0|1, WG_UNI=0|1 (0: the WG_F_UNIFORM plan's 8-lane launches
+ * without the uniform-wave body); unset, the transport kernel plans
  * every batch from its size and the WG_F_UNIFORM hint. Each selects a kernel the product path also takes
  * for some batch; the variants that lost their A/B are not in the library (docs/EXPERIMENTS.md). */
 int wg_ctx_create(int device, uint32_t key_slots, wg_ctx** out);

@@ -130,6 +130,9 @@ struct wg_ctx {
   // alternations); 65,536 x 40 B 37.0 -> 27.1 us per step; 2 (576-B packets too) measured +-0
   // (profiles/r06_slot2_ab.jsonl)
   uint32_t slot2 = 1;
+  // the uniform plan's 8-lane launches bind the kernels whose waves take the uniform-wave body when their
+  // descriptors allow it (k_transport_uni / k_step_uni; WG_UNI=0: k_transport<MODE, 8> / k_step<8>, A/B and parity)
+  bool uni = true;
   // test hook WG_TEST_STEP_FLIP=N (power of two): the k_step launch's seal half writes a wrong tag for every
   // packet whose index is a multiple of N (tests/test_gpu_bench.py: the bench must report verified false)
   uint32_t test_flip = 0;
@@ -646,6 +649,8 @@ int launch_transport(wg_ctx* c, const wg_pkt* desc, uint32_t n, const uint8_t* i
   else if (P.n_long) hipLaunchKernelGGL((wgt::k_transport_mixed<MODE>), dim3(grid), dim3(64 * wgt::TW), 0, s, P);
   else if (G == 16) hipLaunchKernelGGL((wgt::k_transport<MODE, 16>), dim3(grid), dim3(64 * wgt::TW), 0, s, P);
   else if (G == 4) hipLaunchKernelGGL((wgt::k_transport<MODE, 4>), dim3(grid), dim3(64 * wgt::TW), 0, s, P);
+  else if (c->uni && (flags & WG_F_UNIFORM))
+    hipLaunchKernelGGL((wgt::k_transport_uni<MODE>), dim3(grid), dim3(64 * wgt::TW), 0, s, P);
   else hipLaunchKernelGGL((wgt::k_transport<MODE, 8>), dim3(grid), dim3(64 * wgt::TW), 0, s, P);
   const hipError_t e = hipGetLastError();
   record_end(c, s, ev);
@@ -764,6 +769,8 @@ int launch_after_seal(wg_ctx* c, const wg_batch* sb, const wg_batch* ob, hipStre
 #endif
       else if (G == 16) WG_XLAUNCH(wgt::k_step<16>, dim3(gs), blk, 0, s, PS, PO, 0u);
       else if (G == 4) WG_XLAUNCH(wgt::k_step<4>, dim3(gs), blk, 0, s, PS, PO, 0u);
+      else if (c->uni && (sb->flags & WG_F_UNIFORM) && pairs) WG_XLAUNCH((wgt::k_step_uni<4>), dim3(gs), blk, 0, s, PS, PO);
+      else if (c->uni && (sb->flags & WG_F_UNIFORM)) WG_XLAUNCH((wgt::k_step_uni<8>), dim3(gs), blk, 0, s, PS, PO);
       else if (pairs) WG_XLAUNCH((wgt::k_step<8, 4>), dim3(gs), blk, 0, s, PS, PO, 0u);
       else WG_XLAUNCH(wgt::k_step<8>, dim3(gs), blk, 0, s, PS, PO, 0u);
 #undef WG_XLAUNCH
@@ -896,6 +903,10 @@ int wg_ctx_create(int device, uint32_t key_slots, wg_ctx** out) {
   if (const char* e = getenv("WG_UNIFORM16")) c->uniform16 = (uint32_t)std::max(0, atoi(e));
   if (const char* e = getenv("WG_PRIO")) c->prio_mode = atoi(e);
   if (const char* e = getenv("WG_LPT_ONE")) c->lpt_one = atoi(e) != 0;
+  if (const char* e = getenv("WG_UNI")) c->uni = atoi(e) != 0;
+#ifdef WG_DIAG
+  c->uni = false;  // the phase stamps are transport_body's
+#endif
   if (const char* e = getenv("WG_SLOT2")) c->slot2 = (uint32_t)std::max(0, atoi(e));
   if (const char* e = getenv("WG_STREAM_WS")) c->stream_ws_on = atoi(e) != 0;
 #ifdef WG_TEST_HOOKS

@@ -43,6 +43,9 @@
 // cache. Open writes the plaintext in the same pass and zero-fills it again if the tag does
 // not verify (the host per-packet wrappers copy back only verified plaintext, as
 // ChaCha20Poly1305.java:40-56 leaves dst untouched).
+// Uniform waves: in the WG_F_UNIFORM plan's 8-lane kernels (k_transport_uni, k_step_uni) a wave whose slots all
+// hold valid packets of one length, 16-B aligned, under one key runs a smaller body with its uniform state in
+// SGPRs (transport_body_uni, below the general body); every other wave runs transport_body.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -874,6 +877,353 @@ __device__ __forceinline__ void transport_body(const TransportParams& P, uint32_
   WG_PH_STORE(blk * TW + wv);
 }
 
+// ---- the uniform-wave body (8-lane slots, one packet per slot: the WG_F_UNIFORM plan) -----------------
+// Bulk traffic is runs of full-size packets of one session at aligned strides, so every slot of a wave
+// usually holds a valid packet of ONE length, with 16-B aligned input and output, under ONE key. A wave
+// checks exactly that on its own descriptors (ballots, no hint is trusted) and then runs this body INSTEAD
+// of transport_body; a wave that fails any condition runs transport_body unchanged. What is uniform lives
+// in SGPRs and is computed by the scalar unit, whose issue the VALU-bound launch does not pay for: the
+// length and everything derived from it (block, round and MAC chunk counts, the Horner window), the round
+// loop and its trip count, the place of the partial block and of the length block. Left per lane: the
+// packet's offsets and counter, the lane's class (a full 64-B block, the one partial block of the packet,
+// or none), the Horner start chunk. The arithmetic (ChaCha20 block, Poly1305 steps, r-power scan, slot
+// sum, finish) is that of transport_body, bit for bit.
+//
+// Pieces of a packet's MAC and finish, as transport_body computes them:
+// r^1..r^G by a scan over the slot (lane j gets r^(j+1)); R = r^G, W = r^(G-j)
+template <int G>
+__device__ __forceinline__ void rpow_scan(const uint4 rr, uint32_t j, uint32_t R[5], uint32_t W[5]) {
+  uint32_t y[5];
+  poly_r_limbs(rr.x, rr.y, rr.z, rr.w, y);
+#pragma unroll
+  for (uint32_t st = 1; st < G; st <<= 1) {
+    uint32_t z[5], zs[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+      z[i] = st == 1 ? shr_dpp<1>(y[i]) : st == 2 ? shr_dpp<2>(y[i]) : st == 4 ? shr_dpp<4>(y[i]) : shr_dpp<8>(y[i]);
+    poly_scale5(z, zs);
+    if (j >= st) poly_mul(y, z, zs);
+  }
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    R[i] = bcastg<G, G - 1>(y[i]);
+    W[i] = xorg<G - 1>(y[i]);
+  }
+}
+// the slot's sum of the lanes' partials (every lane of the slot ends with it)
+template <int G>
+__device__ __forceinline__ void slot_sum(uint32_t acc[5]) {
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    acc[i] += xor1_dpp(acc[i]);
+    if constexpr (G >= 4) acc[i] += xor2_dpp(acc[i]);
+    if constexpr (G >= 8) acc[i] += xor4_dpp(acc[i]);
+    if constexpr (G == 16) acc[i] += xor8_dpp(acc[i]);
+  }
+}
+// the length block le64(0) || le64(len) as one more Horner step (taken at the finish when it falls outside the
+// last round's window)
+__device__ __forceinline__ void poly_len_block(uint32_t acc[5], const uint32_t R[5], const uint32_t Rs[5], uint32_t len) {
+  poly_mul(acc, R, Rs);
+  acc[2] += (len << 12) & M26;  // le64(len) at bit 64: limb 2 holds bits 52..77
+  acc[3] += len >> 14;
+  acc[4] += 1u << 24;
+}
+// one lane finishes the tag: seal stores it after the ciphertext, open compares all 16 bytes (no early exit).
+// Returns 1 for a tag that does not verify.
+template <int MODE>
+__device__ __forceinline__ uint32_t tag_finish(uint32_t acc[5], const uint4 sv, const uint8_t* in_tag, uint8_t* out_tag) {
+  uint32_t tag[4];
+  poly_finish(acc, sv.x, sv.y, sv.z, sv.w, tag);
+  if constexpr (MODE == WG_MODE_SEAL) {
+    if ((((uintptr_t)out_tag) & 15u) == 0) {
+      *(uint4*)out_tag = make_uint4(tag[0], tag[1], tag[2], tag[3]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) store_u32_any(out_tag + 4 * i, tag[i]);
+    }
+    return 0u;
+  } else {
+    uint32_t diff = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) diff |= load_u32_any(in_tag + 4 * i) ^ tag[i];
+    return diff ? 1u : 0u;
+  }
+}
+// an opened packet's status (lane 0 of the slot; with WG_F_RX_FILTER the receive-side verdict on the plaintext
+// this slot wrote) and, for a tag that did not verify, the scrub of the plaintext written (all lanes of the slot)
+template <int G>
+__device__ __forceinline__ void open_result(const TransportParams& P, uint32_t pkt, uint32_t j, uint32_t bad, bool scrub,
+                                            uint8_t* outp, uint32_t len, uint32_t key_slot) {
+  if (j == 0 && P.status) {
+    uint32_t st = bad ? WG_PKT_BADTAG : WG_PKT_OK;
+    if (!bad && P.rx) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's plaintext stores have landed
+      st = rx_verdict(*P.rx, outp, len, key_slot);
+    }
+    P.status[pkt] = st;
+  }
+  if (scrub) {
+    for (uint32_t i = j; i < len; i += G) outp[i] = 0;
+  }
+}
+
+// the Horner steps of a lane over the round's image (8-lane slots: the lane's chunks are 2 image columns apart;
+// up to four, each tests its chunk against the window's end). first: the packet's first round (scalar), whose
+// first step needs no product (acc is still 0).
+__device__ __forceinline__ void horner_round8(uint32_t acc[5], const uint4* ip, const uint32_t R[5], const uint32_t Rs[5],
+                                              uint32_t c0, uint32_t c_end, bool first) {
+#pragma unroll
+  for (uint32_t t = 0; t < 4u; ++t) {
+    if (c0 + 8u * t < c_end) {
+      const uint4 v = ip[2u * t];
+      if (t != 0 || !first) poly_mul(acc, R, Rs);
+      uint32_t cl[5];
+      poly_block_limbs(v.x, v.y, v.z, v.w, 1u << 24, cl);
+#pragma unroll
+      for (int i = 0; i < 5; ++i) acc[i] += cl[i];
+    }
+  }
+}
+
+// LDS-DMA of chunk Q of this lane's block: 16 B at src + 16 Q to img[64 Q + lane]. The instruction offset is
+// added to the global AND the LDS address, so the LDS base (M0, scalar) is taken back by it.
+template <uint32_t Q>
+__device__ __forceinline__ void dma_chunk(const uint8_t* src, uint4* img) {
+  __builtin_amdgcn_global_load_lds((gbl_cvoid*)src, (lds_void*)((char*)img + (1024u - 16u) * Q), 16, 16 * Q, 0);
+}
+
+// The body of a wave that passed the test (transport_body_uni): len, ks0 scalar; cw0 / cw1 the packet's
+// counter; soff / doff this lane's block of round 0 in the input / output (block 0: 64 B before the packet);
+// live: the lane's slot has a packet (the grid's last wave may have fewer than 8).
+template <int MODE>
+__device__ __forceinline__ void uni_run(const TransportParams& P, uint32_t wg, uint4* const img, SlotRec* const rec,
+                                        uint32_t len, uint32_t ks0, uint32_t cw0, uint32_t cw1, uint64_t soff,
+                                        uint64_t doff, bool live) {
+  constexpr uint32_t G = 8, SH = 3, JM = 7;
+  constexpr uint32_t kNone = 0x40000000u;  // "data block" of a lane whose slot has no packet: never a block of any
+  WG_PH_DECL
+  // everything below that depends only on len is scalar
+  const uint32_t nfull = len >> 6, tail = len & 63u;    // full 64-B blocks, bytes of the partial one
+  const uint32_t rounds = (((len + 63u) >> 6) + 8u) >> 3;  // counter blocks 0..nblk in rounds of 8
+  const uint32_t pround = tail ? (nfull + 1u) >> 3 : ~0u;  // the round that holds the partial block
+  const uint32_t nc = (len + 15u) >> 4, M = nc + 1u, D = G * ((M + JM) >> SH) - M;
+  // the session key: through the scalar cache into ONE record of the wave, which every lane's block reads as a
+  // broadcast
+  uint32_t hc[4];
+  {
+    const uint32_t lane = opaque_lane(), j = lane & JM;
+    const WG_CONST uint32_t* kp = (const WG_CONST uint32_t*)P.keys + 8u * ks0;
+    uint32_t k[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      k[i] = kp[i];
+      asm volatile("" : "+s"(k[i]));
+    }
+    if (lane == 0) {
+      rec[0].key[0] = make_uint4(k[0], k[1], k[2], k[3]);
+      rec[0].key[1] = make_uint4(k[4], k[5], k[6], k[7]);
+    }
+    // the packet's columns 1..3 of the first round, once (lanes 1..3 of the slot feed its blocks)
+    const uint32_t c = j & 3u;
+    hc[0] = c == 1u ? 0x3320646eu : c == 2u ? 0x79622d32u : 0x6b206574u;
+    hc[1] = c == 1u ? k[1] : c == 2u ? k[2] : k[3];
+    hc[2] = c == 1u ? k[5] : c == 2u ? k[6] : k[7];
+    hc[3] = c == 1u ? cw0 : c == 2u ? cw1 : 0u;
+    chacha20_qr(hc[0], hc[1], hc[2], hc[3]);
+  }
+  const uint32_t bj = live ? (opaque_lane() & JM) - 1u : kNone;  // data block of round 0 (block 0's lane wraps)
+  uint32_t acc[5], W[5];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) acc[i] = W[i] = 0;
+  wave_lds_sync();  // the key and the offsets before the lanes read them
+  WG_PH(10);
+
+  for (uint32_t round = 0; round < rounds; ++round) {  // a scalar loop
+    uint32_t x[16];
+    const uint32_t db = G * round + bj;  // this lane's data block (counter block db + 1)
+    {
+      const uint32_t lane = opaque_lane(), j = lane & JM;
+      const uint8_t* src = (P.in + 64u * G * round) + soff;
+      if (db < nfull) {
+        dma_chunk<0>(src, img);
+        dma_chunk<1>(src, img);
+        dma_chunk<2>(src, img);
+        dma_chunk<3>(src, img);
+      }
+      if (round == pround) {  // scalar: at most one lane per slot, chunks holding a valid byte read whole
+        if (db == nfull) {
+          dma_chunk<0>(src, img);
+          if (tail > 16u) dma_chunk<1>(src, img);
+          if (tail > 32u) dma_chunk<2>(src, img);
+          if (tail > 48u) dma_chunk<3>(src, img);
+        }
+      }
+      const uint32_t H[12] = {bcast8<1>(hc[0]), bcast8<1>(hc[1]), bcast8<1>(hc[2]), bcast8<1>(hc[3]),
+                              bcast8<2>(hc[0]), bcast8<2>(hc[1]), bcast8<2>(hc[2]), bcast8<2>(hc[3]),
+                              bcast8<3>(hc[0]), bcast8<3>(hc[1]), bcast8<3>(hc[2]), bcast8<3>(hc[3])};
+      chacha20_block_hoisted(rec[0].key, G * round + j, cw0, cw1, 0u, H, x);
+    }
+    if (round == 0) {  // lane 0 of the slot holds the one-time key r || s
+      const uint32_t lane = opaque_lane(), s = lane >> SH;
+      if ((lane & JM) == 0) {
+        rec[s].R0 = make_uint4(x[0], x[1], x[2], x[3]);  // raw r, replaced by R = r^8 below
+        rec[s].s = make_uint4(x[4], x[5], x[6], x[7]);
+      }
+    }
+    WG_PH(11);
+    // ---- XOR, store, MAC input into the image -------------------------------------------------
+    {
+      const uint32_t lane = opaque_lane();
+      uint8_t* dst = (P.out + 64u * G * round) + doff;
+      if (db < nfull) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the DMA has landed in LDS
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; ++q) {
+          const uint4 v = img[64u * q + lane];
+          const uint4 o = make_uint4(x[4 * q] ^ v.x, x[4 * q + 1] ^ v.y, x[4 * q + 2] ^ v.z, x[4 * q + 3] ^ v.w);
+          if constexpr (MODE == WG_MODE_SEAL) img[64u * q + lane] = o;  // the MAC input is the ciphertext
+          *(uint4*)(dst + 16u * q) = o;
+        }
+      }
+      if (round == pround) {
+        if (db == nfull) {
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          // (once per packet: the chunk arithmetic stays in this lane's registers, as in transport_body; left
+          // scalar, every test of it becomes a loop invariant held in SGPRs across the rounds)
+          uint32_t tl = tail;
+          asm volatile("" : "+v"(tl));
+#pragma unroll
+          for (uint32_t q = 0; q < 4u; ++q) {
+            if (16u * q < tl) {
+              const uint32_t cb = min(16u, tl - 16u * q);  // valid bytes in this chunk
+              uint4 v = img[64u * q + lane];
+              if constexpr (MODE == WG_MODE_OPEN) {
+                if (cb < 16u) {  // the MAC input is the zero-padded ciphertext
+                  v = mask_chunk(v, cb);
+                  img[64u * q + lane] = v;
+                }
+              }
+              uint4 o = make_uint4(x[4 * q] ^ v.x, x[4 * q + 1] ^ v.y, x[4 * q + 2] ^ v.z, x[4 * q + 3] ^ v.w);
+              if constexpr (MODE == WG_MODE_SEAL) {
+                if (cb < 16u) o = mask_chunk(o, cb);
+                img[64u * q + lane] = o;
+              }
+              store_chunk(dst + 16u * q, cb, o, 12u);
+            }
+          }
+        }
+      }
+      // the length block is MAC chunk nc: written into the image by the lane whose counter block holds it
+      if (round == ((nc >> 2) + 1u) >> 3) {
+        if (db == (nc >> 2)) img[64u * (nc & 3u) + lane] = make_uint4(0u, 0u, len, 0u);
+      }
+    }
+    wave_lds_sync();
+    WG_PH(12);
+    if (round == 0) {
+      const uint32_t lane = opaque_lane(), s = lane >> SH, j = lane & JM;
+      uint32_t R[5];
+      rpow_scan<8>(rec[s].R0, j, R, W);
+      if (j == 0) {
+        rec[s].R0 = make_uint4(R[0], R[1], R[2], R[3]);
+        rec[s].R1 = make_uint4(R[4], 5u * R[1], 5u * R[2], 5u * R[3]);
+        rec[s].R2 = make_uint4(5u * R[4], 0u, 0u, 0u);
+      }
+      wave_lds_sync();
+    }
+    WG_PH(13);
+    // ---- Poly1305 over this round's chunks: the window is scalar, its start chunk per lane ------
+    {
+      const uint32_t lane = opaque_lane(), s = lane >> SH, j = lane & JM;
+      const uint32_t c_lo = round ? 4u * G * round - 4u : 0u;
+      const uint32_t c_end = min(nc + 1u, 4u * G * round + 4u * G - 4u);
+      const uint32_t c0 = c_lo + ((j - ((c_lo + D) & JM)) & JM);
+      const uint4* ip = &img[64u * (c0 & 3u) + (lane & ~JM) + ((c0 + 4u) >> 2) - G * round];
+      const uint4 q0 = rec[s].R0, q1 = rec[s].R1, q2 = rec[s].R2;
+      const uint32_t R[5] = {q0.x, q0.y, q0.z, q0.w, q1.x};
+      const uint32_t Rs[5] = {0u, q1.y, q1.z, q1.w, q2.x};
+      horner_round8(acc, ip, R, Rs, c0, c_end, round == 0);
+    }
+    WG_PH(14);
+    wave_lds_sync();  // this round's image before the next round rewrites it
+  }
+
+  // ---- finish: every slot's packet ends with the loop -------------------------------------------
+  {
+    const uint32_t lane = opaque_lane(), s = lane >> SH, j = lane & JM;
+    if (nc >= 4u * G * rounds - 4u) {  // length block not taken in the loop (scalar)
+      if (j == JM) {
+        const uint4 q0 = rec[s].R0, q1 = rec[s].R1, q2 = rec[s].R2;
+        const uint32_t R[5] = {q0.x, q0.y, q0.z, q0.w, q1.x};
+        const uint32_t Rs[5] = {0u, q1.y, q1.z, q1.w, q2.x};
+        poly_len_block(acc, R, Rs, len);
+      }
+    }
+    uint32_t Ws[5];
+    poly_scale5(W, Ws);
+    poly_mul(acc, W, Ws);
+    slot_sum<8>(acc);
+    const uint4 ad = rec[s].addr;
+    const uint8_t* inp = P.in + ((uint64_t)ad.x | ((uint64_t)ad.y << 32));
+    uint8_t* outp = P.out + ((uint64_t)ad.z | ((uint64_t)ad.w << 32));
+    uint32_t bad = 0u;
+    if (live && j == 0) bad = tag_finish<MODE>(acc, rec[s].s, inp + len, outp + len);
+    if constexpr (MODE == WG_MODE_OPEN) {
+      bad = bcast8<0>(bad);
+      if (live) open_result<8>(P, wg * G + s, j, bad, bad != 0u, outp, len, ks0);
+    }
+  }
+  WG_PH(15);
+}
+
+// The test, then one of the two bodies. transport_body has ONE call site, reached with nothing of the test live.
+template <int MODE>
+__device__ __forceinline__ void transport_body_uni(const TransportParams& P, uint32_t blk, uint32_t wv, uint4* const img,
+                                                   SlotRec* const rec, uint32_t& iter) {
+  static_assert(MODE == WG_MODE_SEAL || MODE == WG_MODE_OPEN, "transport modes only");
+  constexpr uint32_t G = 8, SH = 3, JM = 7;
+  const uint32_t wg = blk * TW + wv;
+#ifndef WG_HORNER2  // (the two-chunk Horner keeps other slot records)
+  // the plan the uniform body assumes, from the launch's own parameters (scalar): batch order, one packet per
+  // slot, no issue-priority schedule
+  if (P.order == nullptr && P.prio_step == 0u && P.n <= P.slots) {
+    const uint32_t lane = opaque_lane(), s = lane >> SH, j = lane & JM;
+    const uint32_t g = wg * G + s;
+    const bool live = g < P.n;
+    if (!__any(live)) return;  // a wave past the batch (the grid is whole workgroups)
+    const uint32_t dw = live ? ((const uint32_t*)(P.desc + g))[j] : 0u;
+    const uint32_t d0 = bcast8<0>(dw), d1 = bcast8<1>(dw), d2 = bcast8<2>(dw), d3 = bcast8<3>(dw);
+    const uint32_t cw0 = bcast8<4>(dw), cw1 = bcast8<5>(dw);
+    const uint32_t lv = bcast8<6>(dw), ks = bcast8<7>(dw);
+    const uint64_t in_off = (uint64_t)d0 | ((uint64_t)d1 << 32);
+    const uint64_t out_off = (uint64_t)d2 | ((uint64_t)d3 << 32);
+    const bool valid = transport_valid<MODE>(in_off, out_off, lv, ks, P.max_len, P.key_slots, P.in_size, P.out_size);
+    const uintptr_t ia = (uintptr_t)(P.in + in_off), oa = (uintptr_t)(P.out + out_off);
+    // lane 0 is live (slots take the batch's positions in order): its packet sets the wave's length and key
+    const uint32_t len = __builtin_amdgcn_readfirstlane(lv);
+    const uint32_t ks0 = __builtin_amdgcn_readfirstlane(ks);
+    const bool ok = valid && lv == len && ks == ks0 && ((ia | oa) & 15u) == 0;
+    if (!__any(live && !ok)) {
+      if (j == 0) rec[s].addr = make_uint4(d0, d1, d2, d3);
+      const uint64_t lo = (uint64_t)(64u * j) - 64u;
+      uni_run<MODE>(P, wg, img, rec, len, ks0, cw0, cw1, in_off + lo, out_off + lo, live);
+      return;
+    }
+  }
+#endif
+  transport_body<MODE, 8, false, 0>(P, blk, wv, img, rec, iter);
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(64 * TW) __attribute__((amdgpu_waves_per_eu(8))) k_transport_uni(TransportParams P) {
+  __shared__ uint4 img_[TW][4 * 64];
+  __shared__ SlotRec rec_[TW][8];
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint32_t iter = 0;
+  transport_body_uni<MODE>(P, blockIdx.x, wv, img_[wv], rec_[wv], iter);
+}
+
 // VF: an open whose input and output buffers overlap (the host checks the two ranges): packets
 // that overlap themselves verify first (kVerifyFirst); every other launch takes the one-pass body
 template <int MODE, int G = 8, bool VF = false>
@@ -1056,6 +1406,20 @@ k_step(TransportParams S, TransportParams O, uint32_t test_flip) {
   asm volatile("s_waitcnt vmcnt(0)\n\tbuffer_inv sc0" ::: "memory");
   if constexpr (FLIP) step_test_flip<G>(S, blockIdx.x, wv, test_flip);
   transport_body<WG_MODE_OPEN, G, false, MX>(O, blockIdx.x, wv, img_[wv], rec_[wv], iter);
+}
+
+// k_step for the uniform plan's 8-lane slots: each half decides for itself, wave by wave, between the
+// uniform-wave body and transport_body (transport_body_uni).
+template <int WPE = 8>
+__global__ void __launch_bounds__(64 * TW) __attribute__((amdgpu_waves_per_eu(WPE)))
+k_step_uni(TransportParams S, TransportParams O) {
+  __shared__ uint4 img_[TW][4 * 64];
+  __shared__ SlotRec rec_[TW][8];
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  uint32_t iter = 0;
+  transport_body_uni<WG_MODE_SEAL>(S, blockIdx.x, wv, img_[wv], rec_[wv], iter);
+  asm volatile("s_waitcnt vmcnt(0)\n\tbuffer_inv sc0" ::: "memory");  // as k_step
+  transport_body_uni<WG_MODE_OPEN>(O, blockIdx.x, wv, img_[wv], rec_[wv], iter);
 }
 
 // ---- longest-first order for mixed-length batches (LPT) ----------------------------------
