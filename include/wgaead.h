@@ -556,8 +556,8 @@ int wg_rx_deliver(wg_ctx* ctx, const wg_rx_deliver_batch* batch, void* stream);
  * equal the message's mac1 field, and its mac2 field must be all zero (IncomingInitiation.java:38-40:
  * cookies are not implemented). wg_rx_plan lists the handshake datagrams of a UDP ring; wg_hs_check
  * tests them where they lie and compacts the accepted ones into records, so the host copies back
- * 16 + 160 n_valid bytes and starts Noise on those; it never fetches the ring. X25519, the Noise state
- * machine, cookies and timers stay on the host.
+ * 16 + 160 n_valid bytes and starts Noise on those; it never fetches the ring. The initiations' static DH
+ * follows in the next section; the Noise state machine, cookies and timers stay on the host.
  *
  * wg_blake2s_batch(ctx, desc, n, in, in_size, out, out_size, status, stream): BLAKE2s (RFC 7693),
  *   sequential mode, fanout 1, depth 1, parameter word outlen | keylen << 8 | 0x01010000
@@ -646,6 +646,71 @@ int wg_blake2s_batch(wg_ctx* ctx, const wg_b2s_desc* desc_dev, uint32_t n, const
 int wg_hs_key_set(wg_ctx* ctx, const uint8_t* static_public /* 32 bytes */);
 int wg_hs_reserve(wg_ctx* ctx, uint32_t max_messages);
 int wg_hs_check(wg_ctx* ctx, const wg_hs_batch* batch, void* stream);
+
+/* ---- batched X25519 and the initiations' static DH, on the device ----
+ * mac1 needs only the local static PUBLIC key, so whoever knows it can fill a ring with messages that pass
+ * wg_hs_check; the first thing the responder then does with each initiation is
+ * localKeypair.sharedSecret(remoteEphemeral) (Handshakes.java:210), one Curve25519 ladder per datagram.
+ * wg_x25519_batch is that primitive over descriptors, the analogue of wg_blake2s_batch; wg_hs_dh runs it
+ * over wg_hs_check's records with the static private key of wg_hs_static_set, at the end of the plan ->
+ * check chain. The KDF and hash chain, the AEAD opens of the handshake, the state machine, cookies and
+ * timers stay on the host.
+ *
+ * wg_x25519_batch(ctx, desc, n, in, in_size, out, out_size, status, stream): out[out_off .. out_off + 32)
+ *   = X25519(in[scalar_off .. + 32), in[point_off .. + 32)) as X25519.scalarMult computes it
+ *   (crypto/internal/X25519.java:24-28, 50-60, 96-155; RFC 7748 5): the scalar is clamped on the device
+ *   (k[0] &= 0xF8, k[31] &= 0x7F, k[31] |= 0x40), bit 255 of u is ignored (X25519Field.decode :123-128), a
+ *   non-canonical u (p <= u < 2^255) is accepted and reduced by the arithmetic, and the output is the
+ *   canonical little-endian x2 * z2^(p-2) mod p. WG_X25519_BASE in flags takes the base point u = 9
+ *   (point_off is ignored): what generatePublicKey gives. status[i] is WG_X25519_OK; WG_X25519_ZERO when
+ *   the result is all zero (a low-order point): the 32 zero bytes are written all the same, as
+ *   NoisePrivateKey.sharedSecret (NoisePrivateKey.java:48-52) ignores calculateAgreement's false; or
+ *   WG_X25519_BADDESC when an unknown flag bit is set, _pad is not 0, or the scalar range, the point
+ *   range (unless BASE) or the output range of 32 bytes leaves its buffer (each tested as off <= size &&
+ *   32 <= size - off): a BADDESC leaves the output untouched. Every offset may have any alignment; the
+ *   kernel reads operands as aligned 32-bit words: those that hold at least one byte of a range, never
+ *   another. desc: device, 16-byte aligned. n = 0 is a no-op; out must not overlap in (WG_EINVAL).
+ *   Asynchronous on `stream`, no host state, no scratch, can be captured. One ladder per lane, in
+ *   constant time: no branch, address or loop bound depends on a scalar bit or a field value; lanes with
+ *   a bad descriptor run the same code on dummy operands.
+ *
+ * wg_hs_static_set(ctx, static_private, static_public_out): copies the local static private key into a
+ *   32-byte device buffer that keeps its address for the life of the context (a captured wg_hs_dh reads
+ *   the key when it runs, so a new key needs no re-capture), derives the public key on the device
+ *   (WG_X25519_BASE), returns it in static_public_out (32 bytes; may be NULL) and sets the mac1 key from
+ *   it exactly as wg_hs_key_set(public) would. Synchronous, and ordered after every check or DH queued
+ *   before it. wg_ctx_destroy wipes the private key. A later wg_hs_key_set replaces only the mac1 key.
+ *   wg_hs_dh without a private key returns WG_ENOKEY.
+ *
+ * wg_hs_dh(ctx, b, stream): for every k < min(*n_records, n) (n_records: a device pointer, usually
+ *   &summary->n_valid of the check, read on the device, so plan -> check -> dh run back to back with no
+ *   host read; NULL: all n): a record with len == 148 gives shared[32 k .. 32 k + 32) = X25519(static
+ *   private, msg[8 .. 40)), the initiation's unencrypted_ephemeral (InitiationPacket.java:35-44), and
+ *   dh_status[k] = WG_X25519_OK or WG_X25519_ZERO; a record with len == 92 (a response: the host holds
+ *   that handshake's ephemeral private key, Handshakes.java:125) gives 32 zero bytes and
+ *   WG_X25519_SKIPPED; any other len gives WG_X25519_BADDESC and leaves the 32 bytes untouched. Nothing
+ *   behind min(*n_records, n) entries is written, in either array. No scratch and no reserve call: a
+ *   captured plan + check + dh replays. */
+#define WG_X25519_OK 0u
+#define WG_X25519_BADDESC 1u
+#define WG_X25519_ZERO 2u    /* the result is all zero (a low-order point): written, and flagged */
+#define WG_X25519_SKIPPED 3u /* wg_hs_dh only: the record is a response */
+#define WG_X25519_BASE 1u    /* desc.flags: the point is the base point u = 9; point_off is ignored */
+typedef struct wg_x25519_desc { /* 32 bytes, 16-byte aligned */
+  uint64_t scalar_off, point_off, out_off;
+  uint32_t flags, _pad;
+} wg_x25519_desc;
+typedef struct wg_hs_dh_batch {
+  const wg_hs_record* records; /* device, 16-byte aligned: wg_hs_check's records */
+  const uint32_t* n_records;   /* device: &wg_hs_summary.n_valid; NULL: all n */
+  uint8_t* shared;             /* device, 16-byte aligned, n * 32 bytes */
+  uint32_t* dh_status;         /* device, n entries, WG_X25519_* */
+  uint32_t n, _reserved;
+} wg_hs_dh_batch;
+int wg_x25519_batch(wg_ctx* ctx, const wg_x25519_desc* desc_dev, uint32_t n, const uint8_t* in_dev, uint64_t in_size,
+                    uint8_t* out_dev, uint64_t out_size, uint32_t* status_dev, void* stream);
+int wg_hs_static_set(wg_ctx* ctx, const uint8_t* static_private /* 32 bytes */, uint8_t* static_public_out /* 32 bytes, may be NULL */);
+int wg_hs_dh(wg_ctx* ctx, const wg_hs_dh_batch* batch, void* stream);
 
 int wg_seal1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* pt, uint32_t len, uint8_t* out);
 int wg_open1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* in, uint32_t len, uint8_t* pt);

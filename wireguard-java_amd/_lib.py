@@ -51,6 +51,11 @@ WG_HS_BADMAC1 = 3
 WG_HS_BADMAC2 = 4
 WG_HS_INIT_SIZE = 148
 WG_HS_RESP_SIZE = 92
+WG_X25519_OK = 0
+WG_X25519_BADDESC = 1
+WG_X25519_ZERO = 2
+WG_X25519_SKIPPED = 3
+WG_X25519_BASE = 1
 WG_MAX_FILTERS = 65536
 WG_NO_FILTER = 0xFFFFFFFF
 WG_LEN_INVALID = 0xFFFFFFFF
@@ -167,6 +172,18 @@ class WgHsBatch(ctypes.Structure):
                 ("n", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
 
 
+class WgX25519Desc(ctypes.Structure):
+    """wg_x25519_desc: one scalar multiplication of wg_x25519_batch."""
+    _fields_ = [("scalar_off", ctypes.c_uint64), ("point_off", ctypes.c_uint64), ("out_off", ctypes.c_uint64),
+                ("flags", ctypes.c_uint32), ("_pad", ctypes.c_uint32)]
+
+
+class WgHsDhBatch(ctypes.Structure):
+    """wg_hs_dh_batch: one wg_hs_dh call (device pointers)."""
+    _fields_ = [("records", ctypes.c_void_p), ("n_records", ctypes.c_void_p), ("shared", ctypes.c_void_p),
+                ("dh_status", ctypes.c_void_p), ("n", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
+
+
 class WgCompletion(ctypes.Structure):
     """wg_completion: one reaped packet of a wg_queue."""
     _fields_ = [("user", ctypes.c_uint64), ("counter", ctypes.c_uint64), ("data", ctypes.c_void_p),
@@ -186,6 +203,7 @@ assert ctypes.sizeof(WgRxBatch) == 96 and ctypes.sizeof(WgRxDeliverBatch) == 64
 assert ctypes.sizeof(WgRxSummary) == 16 and ctypes.sizeof(WgRxItem) == 16 and ctypes.sizeof(WgRxDelivered) == 16
 assert ctypes.sizeof(WgB2sDesc) == 32 and ctypes.sizeof(WgHsRecord) == 160 and ctypes.sizeof(WgHsSummary) == 16
 assert ctypes.sizeof(WgHsBatch) == 80
+assert ctypes.sizeof(WgX25519Desc) == 32 and ctypes.sizeof(WgHsDhBatch) == 40
 assert ctypes.sizeof(WgPkt) == 32 and ctypes.sizeof(WgAeadDesc) == 64 and ctypes.sizeof(WgPrefix) == 18
 
 # (name, restype, argtypes) for every symbol include/wgaead.h declares
@@ -231,6 +249,9 @@ SIGNATURES = [
     ("wg_hs_key_set", _I, [_VP, _VP]),
     ("wg_hs_reserve", _I, [_VP, _U32]),
     ("wg_hs_check", _I, [_VP, ctypes.POINTER(WgHsBatch), _VP]),
+    ("wg_x25519_batch", _I, [_VP, _VP, _U32, _VP, _U64, _VP, _U64, _VP, _VP]),
+    ("wg_hs_static_set", _I, [_VP, _VP, _VP]),
+    ("wg_hs_dh", _I, [_VP, ctypes.POINTER(WgHsDhBatch), _VP]),
     ("wg_seal1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_open1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_pp_config", _I, [_VP, _U32, _U32]),

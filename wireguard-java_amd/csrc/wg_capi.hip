@@ -175,7 +175,7 @@ struct wg_ctx {
   RxState* rx = nullptr;  // receive-side checks (wg_rx.hip)
   TxState* tx = nullptr;  // transmit-side planning: send counters, peers, routes (wg_tx.hip)
   RxPlanState* rxp = nullptr;  // receive-side planning: session table, scratch (wg_rxplan.hip)
-  HsState* hs = nullptr;  // handshake admission: mac1 key, scratch (wg_hs.hip)
+  HsState* hs = nullptr;  // handshake: mac1 key, static private key, scratch (wg_hs.hip, wg_x25519.hip)
   // timing
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -809,6 +809,7 @@ int launch_after_seal(wg_ctx* c, const wg_batch* sb, const wg_batch* ob, hipStre
 #include "wg_tx.hip"
 #include "wg_rxplan.hip"
 #include "wg_hs.hip"
+#include "wg_x25519.hip"
 
 extern "C" {
 
@@ -821,7 +822,7 @@ int wg_diag_stamps(void* dev_buf) {
 #endif
 
 const char* wg_last_error(void) { return g_err.c_str(); }
-const char* wg_version(void) { return "wgaead 0.3.0 gfx950"; }
+const char* wg_version(void) { return "wgaead 0.4.0 gfx950"; }
 
 int wg_ctx_set_kernel(wg_ctx* c, const char* name, uint32_t lanes, uint32_t variant) {
   (void)lanes;

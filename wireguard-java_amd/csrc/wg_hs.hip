@@ -37,9 +37,11 @@ namespace {
 
 struct HsState {
   DevBuf d_key;    // the mac1 key, 32 B (fixed address)
-  DevBuf d_stage;  // wg_hs_key_set: descriptor, "mac1----" || public key, status
+  DevBuf d_priv;   // the static private key, 32 B (fixed address; wg_hs_static_set, wg_x25519.hip)
+  DevBuf d_stage;  // wg_hs_key_set: descriptor, "mac1----" || public key, status; wg_hs_static_set: [128, 196)
   DevBuf d_part;   // per range of 256 list positions: {valid, init, resp, rejected}, then their exclusive prefixes
   bool has_key = false;
+  bool has_priv = false;
   hipEvent_t ev = nullptr;  // last use of the scratch, and its stream
   hipStream_t ev_stream = (hipStream_t)-1;
 };
@@ -49,15 +51,17 @@ int hs_get(wg_ctx* c, HsState** out) {
   if (!c->hs) {
     auto t = std::make_unique<HsState>();
     int rc;
-    if ((rc = t->d_key.ensure(32)) != WG_OK || (rc = t->d_stage.ensure(256)) != WG_OK) {
-      for (DevBuf* b : {&t->d_key, &t->d_stage}) b->release();
+    if ((rc = t->d_key.ensure(32)) != WG_OK || (rc = t->d_priv.ensure(32)) != WG_OK ||
+        (rc = t->d_stage.ensure(256)) != WG_OK) {
+      for (DevBuf* b : {&t->d_key, &t->d_priv, &t->d_stage}) b->release();
       return rc;
     }
     hipError_t e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipMemsetAsync(t->d_key.p, 0, 32, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_priv.p, 0, 32, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
-      for (DevBuf* b : {&t->d_key, &t->d_stage}) b->release();
+      for (DevBuf* b : {&t->d_key, &t->d_priv, &t->d_stage}) b->release();
       if (t->ev) (void)hipEventDestroy(t->ev);
       return fail(WG_EDEVICE, "handshake state: %s", hipGetErrorString(e));
     }
@@ -70,12 +74,13 @@ int hs_get(wg_ctx* c, HsState** out) {
 void hs_free(wg_ctx* c) {
   if (!c->hs) return;
   HsState* t = c->hs;
-  if (t->d_key.p) {  // the key is wiped, like the key table
+  if (t->d_key.p) {  // the keys are wiped, like the key table
     (void)hipDeviceSynchronize();
     (void)hipMemsetAsync(t->d_key.p, 0, 32, c->stream);
+    if (t->d_priv.p) (void)hipMemsetAsync(t->d_priv.p, 0, 32, c->stream);
     (void)hipStreamSynchronize(c->stream);
   }
-  for (DevBuf* b : {&t->d_key, &t->d_stage, &t->d_part}) b->release();
+  for (DevBuf* b : {&t->d_key, &t->d_priv, &t->d_stage, &t->d_part}) b->release();
   if (t->ev) (void)hipEventDestroy(t->ev);
   delete t;
   c->hs = nullptr;
@@ -361,6 +366,29 @@ int b2s_launch(const wg_b2s_desc* desc, uint32_t n, const uint8_t* in, uint64_t 
   return WG_OK;
 }
 
+// the mac1 key of `static_public` into the fixed key buffer (wg_hs_key_set; wg_hs_static_set with the public key it
+// derived). Caller holds c->mu.
+int hs_mac1_key_set(wg_ctx* c, HsState* t, const uint8_t* static_public) {
+  int rc;
+  // stage: [0, 32) the descriptor, [32, 72) "mac1----" || public key (InitiationPacket.java:111-115), [96, 100) status
+  uint8_t host[128] = {0};
+  wg_b2s_desc d{};
+  d.in_off = 32;
+  d.len = 40;
+  d.outlen = 32;
+  memcpy(host, &d, sizeof d);
+  memcpy(host + 32, "mac1----", 8);
+  memcpy(host + 40, static_public, 32);
+  HIPTRY(hipDeviceSynchronize());  // no check queued earlier (on any stream) may still read the old key
+  uint8_t* st = (uint8_t*)t->d_stage.p;
+  HIPTRY(hipMemcpyAsync(st, host, sizeof host, hipMemcpyHostToDevice, c->stream));
+  if ((rc = b2s_launch((const wg_b2s_desc*)st, 1, st, 128, (uint8_t*)t->d_key.p, 32, (uint32_t*)(st + 96), c->stream)) != WG_OK)
+    return rc;
+  HIPTRY(hipStreamSynchronize(c->stream));
+  t->has_key = true;
+  return WG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -384,23 +412,7 @@ int wg_hs_key_set(wg_ctx* c, const uint8_t* static_public) {
   HsState* t;
   int rc;
   if ((rc = hs_get(c, &t)) != WG_OK) return rc;
-  // stage: [0, 32) the descriptor, [32, 72) "mac1----" || public key (InitiationPacket.java:111-115), [96, 100) status
-  uint8_t host[128] = {0};
-  wg_b2s_desc d{};
-  d.in_off = 32;
-  d.len = 40;
-  d.outlen = 32;
-  memcpy(host, &d, sizeof d);
-  memcpy(host + 32, "mac1----", 8);
-  memcpy(host + 40, static_public, 32);
-  HIPTRY(hipDeviceSynchronize());  // no check queued earlier (on any stream) may still read the old key
-  uint8_t* st = (uint8_t*)t->d_stage.p;
-  HIPTRY(hipMemcpyAsync(st, host, sizeof host, hipMemcpyHostToDevice, c->stream));
-  if ((rc = b2s_launch((const wg_b2s_desc*)st, 1, st, 128, (uint8_t*)t->d_key.p, 32, (uint32_t*)(st + 96), c->stream)) != WG_OK)
-    return rc;
-  HIPTRY(hipStreamSynchronize(c->stream));
-  t->has_key = true;
-  return WG_OK;
+  return hs_mac1_key_set(c, t, static_public);
 }
 
 int wg_hs_reserve(wg_ctx* c, uint32_t max_messages) {

@@ -50,6 +50,18 @@ def pack_b2s_desc(in_off, out_off, key_off, length, outlen, keylen) -> np.ndarra
     return d
 
 
+WG_X25519_DTYPE = np.dtype([("scalar_off", "<u8"), ("point_off", "<u8"), ("out_off", "<u8"), ("flags", "<u4"),
+                            ("_pad", "<u4")])
+
+
+def pack_x25519_desc(scalar_off, point_off, out_off, flags=0) -> np.ndarray:
+    """Build a wg_x25519_desc array (numpy structured) from per-operand columns."""
+    n = len(np.atleast_1d(scalar_off))
+    d = np.zeros(n, WG_X25519_DTYPE)
+    d["scalar_off"], d["point_off"], d["out_off"], d["flags"] = scalar_off, point_off, out_off, flags
+    return d
+
+
 def desc_as_int64(d: np.ndarray) -> np.ndarray:
     """wg_pkt array viewed as int64 [n, 4] (for torch.from_numpy)."""
     d = np.ascontiguousarray(d)
@@ -405,6 +417,77 @@ class Engine:
                         host_list.data_ptr() if host_list is not None else None, n_list, hs_status.data_ptr(),
                         records.data_ptr(), hs_summary.data_ptr(), pkt_off.shape[0], 0)
         L.check(self._lib.wg_hs_check(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    # ---- X25519 (wg_x25519_batch / wg_hs_static_set / wg_hs_dh) -------------------------------
+    def x25519(self, desc, inp, out, status, stream: int | None = None) -> None:
+        """wg_x25519_batch over torch tensors: desc int64 [n, 4] (wg_x25519_desc records, pack_x25519_desc),
+        inp / out uint8 (device, not overlapping), status int32 [n] (WG_X25519_*). Scalars and points are
+        read from inp; the scalars are clamped on the device."""
+        n = desc.shape[0]
+        L.check(self._lib.wg_x25519_batch(self.ctx, desc.data_ptr(), n, inp.data_ptr(), inp.numel(), out.data_ptr(),
+                                          out.numel(), status.data_ptr(),
+                                          stream if stream is not None else _torch_stream()))
+
+    def x25519_host(self, pairs) -> list:
+        """X25519 of host byte strings through one wg_x25519_batch call: pairs = [(scalar, point)], a point of
+        None is the base point; returns [(32 bytes, WG_X25519_* status)]. The device copies of the scalars are
+        zeroed before it returns. For the noise mirror and tests; a data path keeps its bytes on the device
+        and calls x25519()."""
+        import torch
+        if not pairs:
+            return []
+        dev = torch.device("cuda", self.device)
+        n = len(pairs)
+        buf = bytearray(64 * n)
+        flags = np.zeros(n, np.uint32)
+        for k, (scalar, point) in enumerate(pairs):
+            if len(scalar) != 32 or (point is not None and len(point) != 32):
+                raise L.WgError(L.WG_EINVAL, "X25519 scalars and points are 32 bytes")
+            buf[64 * k:64 * k + 32] = bytes(scalar)
+            if point is None:
+                flags[k] = L.WG_X25519_BASE
+            else:
+                buf[64 * k + 32:64 * k + 64] = bytes(point)
+        at = 64 * np.arange(n, dtype=np.uint64)
+        d = pack_x25519_desc(at, at + np.uint64(32), 32 * np.arange(n, dtype=np.uint64), flags)
+        d_desc = torch.from_numpy(desc_as_int64(d)).to(dev)
+        d_in = torch.from_numpy(np.frombuffer(bytes(buf), np.uint8).copy()).to(dev)
+        d_out = torch.zeros(32 * n, dtype=torch.uint8, device=dev)
+        d_st = torch.zeros(n, dtype=torch.int32, device=dev)
+        st = _torch_stream()
+        try:
+            self.x25519(d_desc, d_in, d_out, d_st, stream=st)
+            self.sync(st)
+        finally:
+            d_in.zero_()
+            torch.cuda.synchronize(dev)
+            buf[:] = bytes(len(buf))
+        status = d_st.cpu().numpy().tolist()
+        if L.WG_X25519_BADDESC in status:
+            raise L.WgError(L.WG_EINVAL, "wg_x25519_batch refused a descriptor")
+        out = d_out.cpu().numpy().tobytes()
+        return [(out[32 * k:32 * k + 32], int(status[k])) for k in range(n)]
+
+    def hs_static_set(self, static_private) -> bytes:
+        """wg_hs_static_set: the local static private key (32 bytes) into its device buffer; returns the public
+        key, derived on the device, and sets the mac1 key from it as hs_key_set(public) would."""
+        priv = np.frombuffer(bytes(static_private), np.uint8).copy()
+        if priv.size != 32:
+            raise L.WgError(L.WG_EINVAL, f"static private key of {priv.size} bytes")
+        pub = np.zeros(32, np.uint8)
+        try:
+            L.check(self._lib.wg_hs_static_set(self.ctx, priv.ctypes.data, pub.ctypes.data))
+        finally:
+            priv[:] = 0
+        return pub.tobytes()
+
+    def hs_dh(self, records, hs_summary, shared, dh_status, stream: int | None = None) -> None:
+        """wg_hs_dh over torch tensors: records uint8 [n, 160] and hs_summary int32 [4] as hs_check() wrote
+        them (the record count, n_valid, is read on the device: check and dh run back to back on one stream;
+        hs_summary None: all n records), shared uint8 [n, 32] or [n * 32], dh_status int32 [n] (WG_X25519_*)."""
+        n_records = hs_summary.data_ptr() + L.WgHsSummary.n_valid.offset if hs_summary is not None else None
+        b = L.WgHsDhBatch(records.data_ptr(), n_records, shared.data_ptr(), dh_status.data_ptr(), records.shape[0], 0)
+        L.check(self._lib.wg_hs_dh(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
 
     def set_receivers(self, receivers) -> None:
         """wg_ctx_set_receivers: device tensor of receiver_index per key slot for

@@ -42,6 +42,9 @@ public final class WgAead {
 	/** wg_blake2s_batch and wg_hs_check outcomes (IncomingInitiation.java:24-40, IncomingResponse.java:20-36). */
 	public static final int WG_B2S_OK = 0, WG_B2S_BADDESC = 1;
 	public static final int WG_HS_OK = 0, WG_HS_BADLEN = 1, WG_HS_BADTYPE = 2, WG_HS_BADMAC1 = 3, WG_HS_BADMAC2 = 4;
+	/** wg_x25519_batch and wg_hs_dh outcomes; WG_X25519_BASE is a descriptor flag (the base point u = 9). */
+	public static final int WG_X25519_OK = 0, WG_X25519_BADDESC = 1, WG_X25519_ZERO = 2, WG_X25519_SKIPPED = 3;
+	public static final int WG_X25519_BASE = 1;
 	public static final long AEAD_DESC_SIZE = 64, PKT_DESC_SIZE = 32, BATCH_SIZE = 64, TX_BATCH_SIZE = 88,
 		RX_BATCH_SIZE = 96, RX_DELIVER_BATCH_SIZE = 64, RX_SUMMARY_SIZE = 16, RX_ITEM_SIZE = 16, RX_DELIVERED_SIZE = 16,
 		B2S_DESC_SIZE = 32, HS_BATCH_SIZE = 80, HS_RECORD_SIZE = 160, HS_SUMMARY_SIZE = 16;
@@ -51,7 +54,8 @@ public final class WgAead {
 		FILTER_SET, SLOT_FILTERS_SET, REPLAY_ENABLE, REPLAY_RESET, RX_CHECK, DUPLEX_BATCH, QUEUE_CREATE,
 		QUEUE_DESTROY, SUBMIT_SEAL, SUBMIT_OPEN, SUBMIT_SEAL_N, SUBMIT_OPEN_N, REAP, REAP_DONE, QUEUE_SUBMIT_TIMEOUT,
 		NUMA_NODE, TX_PEERS_SET, ROUTES_SET, TX_COUNTERS_SET, TX_COUNTERS_GET, TX_RESERVE, TX_PLAN,
-		RX_SESSIONS_SET, RX_RESERVE, RX_PLAN, RX_DELIVER, BLAKE2S_BATCH, HS_KEY_SET, HS_RESERVE, HS_CHECK;
+		RX_SESSIONS_SET, RX_RESERVE, RX_PLAN, RX_DELIVER, BLAKE2S_BATCH, HS_KEY_SET, HS_RESERVE, HS_CHECK,
+		X25519_BATCH, HS_STATIC_SET, HS_DH;
 
 	/** The process-wide context (one HIP device, its stream and its device key table). */
 	static final MemorySegment CTX;
@@ -129,6 +133,13 @@ public final class WgAead {
 		HS_KEY_SET = down(linker, symbols, "wg_hs_key_set", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS));
 		HS_RESERVE = down(linker, symbols, "wg_hs_reserve", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT));
 		HS_CHECK = down(linker, symbols, "wg_hs_check", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
+		// batched X25519 (X25519.java:96-155) over wg_x25519_desc entries of 32 bytes, the static private key
+		// into its device buffer (returns the public key), and the static DH of the initiations among
+		// wg_hs_check's records (Handshakes.java:210); wg_hs_dh takes one wg_hs_dh_batch struct of 40 bytes
+		X25519_BATCH = down(linker, symbols, "wg_x25519_batch", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS,
+			JAVA_INT, ADDRESS, JAVA_LONG, ADDRESS, JAVA_LONG, ADDRESS, ADDRESS));
+		HS_STATIC_SET = down(linker, symbols, "wg_hs_static_set", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
+		HS_DH = down(linker, symbols, "wg_hs_dh", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
 		// outgoing seal + incoming open in one launch (two wg_batch structs of 64 bytes)
 		DUPLEX_BATCH = down(linker, symbols, "wg_duplex_batch", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS,
 			ADDRESS));
