@@ -557,7 +557,8 @@ int wg_rx_deliver(wg_ctx* ctx, const wg_rx_deliver_batch* batch, void* stream);
  * cookies are not implemented). wg_rx_plan lists the handshake datagrams of a UDP ring; wg_hs_check
  * tests them where they lie and compacts the accepted ones into records, so the host copies back
  * 16 + 160 n_valid bytes and starts Noise on those; it never fetches the ring. The initiations' static DH
- * follows in the next section; the Noise state machine, cookies and timers stay on the host.
+ * and the open of their encrypted static follow in the next two sections; the rest of the Noise state
+ * machine, cookies and timers stay on the host.
  *
  * wg_blake2s_batch(ctx, desc, n, in, in_size, out, out_size, status, stream): BLAKE2s (RFC 7693),
  *   sequential mode, fanout 1, depth 1, parameter word outlen | keylen << 8 | 0x01010000
@@ -653,8 +654,9 @@ int wg_hs_check(wg_ctx* ctx, const wg_hs_batch* batch, void* stream);
  * localKeypair.sharedSecret(remoteEphemeral) (Handshakes.java:210), one Curve25519 ladder per datagram.
  * wg_x25519_batch is that primitive over descriptors, the analogue of wg_blake2s_batch; wg_hs_dh runs it
  * over wg_hs_check's records with the static private key of wg_hs_static_set, at the end of the plan ->
- * check chain. The KDF and hash chain, the AEAD opens of the handshake, the state machine, cookies and
- * timers stay on the host.
+ * check chain. The KDF and hash chain up to the initiator's static key and the open of encrypted_static
+ * follow in the next section (wg_hs_open); the response, the state machine, cookies and timers stay on the
+ * host.
  *
  * wg_x25519_batch(ctx, desc, n, in, in_size, out, out_size, status, stream): out[out_off .. out_off + 32)
  *   = X25519(in[scalar_off .. + 32), in[point_off .. + 32)) as X25519.scalarMult computes it
@@ -711,6 +713,89 @@ int wg_x25519_batch(wg_ctx* ctx, const wg_x25519_desc* desc_dev, uint32_t n, con
                     uint8_t* out_dev, uint64_t out_size, uint32_t* status_dev, void* stream);
 int wg_hs_static_set(wg_ctx* ctx, const uint8_t* static_private /* 32 bytes */, uint8_t* static_public_out /* 32 bytes, may be NULL */);
 int wg_hs_dh(wg_ctx* ctx, const wg_hs_dh_batch* batch, void* stream);
+
+/* ---- the initiations' encrypted static, opened on the device ----
+ * What rejects a forged initiation comes after mac1 and the DH: Handshakes.decryptRemoteStatic
+ * (Handshakes.java:201-237; per initiation from PeerList.java:80 and SessionManager.java:212). wg_hs_open is
+ * that step over wg_hs_check's records and wg_hs_dh's secrets, bit-exact, with the peer lookup behind it:
+ * the host receives the authenticated initiations, by peer, with the Noise state the responder goes on
+ * from, and reads nothing in between. With H = BLAKE2s-256, KDFn(salt, ikm) = Crypto.deriveKey(salt, ikm,
+ * n) (HKDF over HMAC-BLAKE2s, 64-byte block, empty info: Crypto.java:39-99), CK0 = INITIAL_CHAIN_KEY, H0 =
+ * INITIAL_HASH (Handshakes.java:20-37), E = msg[8 .. 40), es = msg[40 .. 88), ets = msg[88 .. 116)
+ * (InitiationPacket.java:21-45) and ss = shared[32 k .. 32 k + 32):
+ *     h  = H(H(H0 || S_pub) || E)      ck = KDF1(CK0, E)
+ *     k  = KDF2(ck, ss)                ck = KDF1(ck, ss)
+ *     remote_static = ChaCha20-Poly1305-open(k, nonce 0^12, aad = h, es), else WG_HS_OPEN_BADAUTH
+ *     h  = H(h || es)
+ *     known peer: ck = KDF1(ck, X25519(S_priv, remote_static))
+ *     h  = H(h || ets)
+ *   (state.chainKey and decryptRemoteStatic's local chainKey are one array, Handshakes.java:203 and
+ *   :314-316, so this is the ordinary Noise IK chain.) Like the reference, the step never opens ets: its 28
+ *   bytes are only mixed into the hash (:233-234). A record whose dh_status is WG_X25519_ZERO goes through
+ *   like any other (the reference ignores the agreement's false).
+ *
+ * wg_hs_peers_set(ctx, publics, n): replaces the whole table of the peers' static public keys (host
+ *   pointer, 32 n bytes) and computes, in one launch, each peer's X25519(static private key, public key),
+ *   which stays on the device. A peer is named by its position in `publics`. Keys are compared in all 32
+ *   bytes (bit 255 as the byte it is); two equal keys are WG_EINVAL and nothing changes. n = 0 empties the
+ *   table. Without a private key: WG_ENOKEY. The table sits behind a header at a fixed device address: a
+ *   captured open sees the new table without re-capture. Synchronous, and ordered after everything queued
+ *   before it. A later wg_hs_static_set recomputes the stored peers' secrets under the new key, and keeps
+ *   H(H0 || S_pub) beside the mac1 key; wg_hs_key_set touches neither. wg_ctx_destroy wipes the secrets.
+ *
+ * wg_hs_open(ctx, b, stream): for every k < min(*n_records, n) (n_records as in wg_hs_dh; NULL: all n),
+ *   with len = records[k].len and ds = dh_status[k], in this order:
+ *   1. len == 92: WG_HS_OPEN_SKIPPED (a response). 2. len != 148: WG_HS_OPEN_BADDESC.
+ *   3. ds == WG_X25519_SKIPPED: WG_HS_OPEN_SKIPPED. 4. ds is neither WG_X25519_OK nor WG_X25519_ZERO:
+ *   WG_HS_OPEN_BADDESC. 5. the tag of es does not verify (all 16 bytes compared, no early exit):
+ *   WG_HS_OPEN_BADAUTH. 6. remote_static is in the table: WG_HS_OPEN_OK, else WG_HS_OPEN_NEWPEER (the
+ *   reference adds such a peer, PeerList.java:85-86: the host decides).
+ *   open_status[k] is written for those k and nothing behind them. inits[0 .. n_emitted) is the stable
+ *   compaction, in record order, of the OK and NEWPEER records: {index = records[k].index, record = k,
+ *   sender_index = msg[4 .. 8), peer = the position in the table or WG_HS_NOPEER, remote_ephemeral = E,
+ *   remote_static, hash = the final h, chain_key = the final ck; for a NEWPEER the ck BEFORE the
+ *   static-static step, which one ladder and one KDF1 on the host finish}. Every byte of a written entry is
+ *   defined; nothing behind n_emitted entries is touched, and nothing but its status is written for any
+ *   other record. summary = {n_emitted, n_known (OK), n_badauth, n_skipped}. n = 0 is a no-op. Works with an
+ *   empty or never-set table (every authentic initiation is NEWPEER). Without a private key: WG_ENOKEY.
+ *   records, shared, inits: 16-byte aligned; summary: 8; the others: 4. An output that overlaps another
+ *   output or an input: WG_EINVAL. Scratch (112 bytes per record) is sized by wg_hs_reserve; a call that
+ *   needs more allocates it, except on a capturing stream (WG_EINVAL: reserve first). Three launches
+ *   (open, scan, emit) with no wait between workgroups and nothing about a call on the host: a captured
+ *   plan + check + dh + open replays, and wg_hs_peers_set / wg_hs_static_set between replays need no
+ *   re-capture. One record per lane; no branch, address or loop bound depends on ss, on a derived key or
+ *   on a static-static secret. */
+#define WG_HS_OPEN_OK 0u
+#define WG_HS_OPEN_NEWPEER 1u /* authentic; the static key is not in the peer table */
+#define WG_HS_OPEN_BADAUTH 2u
+#define WG_HS_OPEN_SKIPPED 3u /* a response, or dh_status is WG_X25519_SKIPPED */
+#define WG_HS_OPEN_BADDESC 4u /* any other record length, or dh_status is WG_X25519_BADDESC */
+#define WG_HS_NOPEER 0xFFFFFFFFu
+typedef struct wg_hs_init { /* 144 bytes */
+  uint32_t index;        /* batch index of the datagram */
+  uint32_t record;       /* position in wg_hs_check's records */
+  uint32_t sender_index; /* msg[4 .. 8) */
+  uint32_t peer;         /* position in wg_hs_peers_set's table, or WG_HS_NOPEER */
+  uint8_t remote_ephemeral[32];
+  uint8_t remote_static[32];
+  uint8_t hash[32];
+  uint8_t chain_key[32];
+} wg_hs_init;
+typedef struct wg_hs_open_summary {
+  uint32_t n_emitted, n_known, n_badauth, n_skipped;
+} wg_hs_open_summary;
+typedef struct wg_hs_open_batch {
+  const wg_hs_record* records; /* device, 16-byte aligned: wg_hs_check's records */
+  const uint32_t* n_records;   /* device: &wg_hs_summary.n_valid; NULL: all n */
+  const uint8_t* shared;       /* device, 16-byte aligned, n * 32 bytes: wg_hs_dh's */
+  const uint32_t* dh_status;   /* device, n entries: wg_hs_dh's */
+  uint32_t* open_status;       /* device, n entries, WG_HS_OPEN_* */
+  wg_hs_init* inits;           /* device, 16-byte aligned, n entries */
+  wg_hs_open_summary* summary; /* device, 16 bytes, 8-byte aligned */
+  uint32_t n, _reserved;
+} wg_hs_open_batch;
+int wg_hs_peers_set(wg_ctx* ctx, const uint8_t* publics_host /* 32 n bytes */, uint32_t n);
+int wg_hs_open(wg_ctx* ctx, const wg_hs_open_batch* batch, void* stream);
 
 int wg_seal1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* pt, uint32_t len, uint8_t* out);
 int wg_open1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* in, uint32_t len, uint8_t* pt);

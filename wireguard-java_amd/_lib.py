@@ -56,6 +56,12 @@ WG_X25519_BADDESC = 1
 WG_X25519_ZERO = 2
 WG_X25519_SKIPPED = 3
 WG_X25519_BASE = 1
+WG_HS_OPEN_OK = 0
+WG_HS_OPEN_NEWPEER = 1
+WG_HS_OPEN_BADAUTH = 2
+WG_HS_OPEN_SKIPPED = 3
+WG_HS_OPEN_BADDESC = 4
+WG_HS_NOPEER = 0xFFFFFFFF
 WG_MAX_FILTERS = 65536
 WG_NO_FILTER = 0xFFFFFFFF
 WG_LEN_INVALID = 0xFFFFFFFF
@@ -184,6 +190,27 @@ class WgHsDhBatch(ctypes.Structure):
                 ("dh_status", ctypes.c_void_p), ("n", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
 
 
+class WgHsInit(ctypes.Structure):
+    """wg_hs_init: one authenticated initiation of wg_hs_open."""
+    _fields_ = [("index", ctypes.c_uint32), ("record", ctypes.c_uint32), ("sender_index", ctypes.c_uint32),
+                ("peer", ctypes.c_uint32), ("remote_ephemeral", ctypes.c_uint8 * 32),
+                ("remote_static", ctypes.c_uint8 * 32), ("hash", ctypes.c_uint8 * 32),
+                ("chain_key", ctypes.c_uint8 * 32)]
+
+
+class WgHsOpenSummary(ctypes.Structure):
+    """wg_hs_open_summary: totals of one wg_hs_open call."""
+    _fields_ = [("n_emitted", ctypes.c_uint32), ("n_known", ctypes.c_uint32), ("n_badauth", ctypes.c_uint32),
+                ("n_skipped", ctypes.c_uint32)]
+
+
+class WgHsOpenBatch(ctypes.Structure):
+    """wg_hs_open_batch: one wg_hs_open call (device pointers)."""
+    _fields_ = [("records", ctypes.c_void_p), ("n_records", ctypes.c_void_p), ("shared", ctypes.c_void_p),
+                ("dh_status", ctypes.c_void_p), ("open_status", ctypes.c_void_p), ("inits", ctypes.c_void_p),
+                ("summary", ctypes.c_void_p), ("n", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
+
+
 class WgCompletion(ctypes.Structure):
     """wg_completion: one reaped packet of a wg_queue."""
     _fields_ = [("user", ctypes.c_uint64), ("counter", ctypes.c_uint64), ("data", ctypes.c_void_p),
@@ -204,6 +231,7 @@ assert ctypes.sizeof(WgRxSummary) == 16 and ctypes.sizeof(WgRxItem) == 16 and ct
 assert ctypes.sizeof(WgB2sDesc) == 32 and ctypes.sizeof(WgHsRecord) == 160 and ctypes.sizeof(WgHsSummary) == 16
 assert ctypes.sizeof(WgHsBatch) == 80
 assert ctypes.sizeof(WgX25519Desc) == 32 and ctypes.sizeof(WgHsDhBatch) == 40
+assert ctypes.sizeof(WgHsInit) == 144 and ctypes.sizeof(WgHsOpenSummary) == 16 and ctypes.sizeof(WgHsOpenBatch) == 64
 assert ctypes.sizeof(WgPkt) == 32 and ctypes.sizeof(WgAeadDesc) == 64 and ctypes.sizeof(WgPrefix) == 18
 
 # (name, restype, argtypes) for every symbol include/wgaead.h declares
@@ -252,6 +280,8 @@ SIGNATURES = [
     ("wg_x25519_batch", _I, [_VP, _VP, _U32, _VP, _U64, _VP, _U64, _VP, _VP]),
     ("wg_hs_static_set", _I, [_VP, _VP, _VP]),
     ("wg_hs_dh", _I, [_VP, ctypes.POINTER(WgHsDhBatch), _VP]),
+    ("wg_hs_peers_set", _I, [_VP, _VP, _U32]),
+    ("wg_hs_open", _I, [_VP, ctypes.POINTER(WgHsOpenBatch), _VP]),
     ("wg_seal1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_open1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_pp_config", _I, [_VP, _U32, _U32]),

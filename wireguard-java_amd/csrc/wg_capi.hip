@@ -175,7 +175,7 @@ struct wg_ctx {
   RxState* rx = nullptr;  // receive-side checks (wg_rx.hip)
   TxState* tx = nullptr;  // transmit-side planning: send counters, peers, routes (wg_tx.hip)
   RxPlanState* rxp = nullptr;  // receive-side planning: session table, scratch (wg_rxplan.hip)
-  HsState* hs = nullptr;  // handshake: mac1 key, static private key, scratch (wg_hs.hip, wg_x25519.hip)
+  HsState* hs = nullptr;  // handshake: mac1 key, static private key, peers, scratch (wg_hs.hip, wg_x25519.hip, wg_hs_open.hip)
   // timing
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -810,6 +810,7 @@ int launch_after_seal(wg_ctx* c, const wg_batch* sb, const wg_batch* ob, hipStre
 #include "wg_rxplan.hip"
 #include "wg_hs.hip"
 #include "wg_x25519.hip"
+#include "wg_hs_open.hip"
 
 extern "C" {
 

@@ -35,11 +35,26 @@
 
 namespace {
 
+struct HsPeerHdr {  // at a fixed device address; wg_hs_peers_set rewrites it (and may move what it names): wg_hs_open.hip
+  const uint32_t* slots;   // capacity x (peer + 1), 0: empty
+  const uint8_t* publics;  // 32 B per peer: the static public keys, in the caller's order
+  const uint8_t* secrets;  // 32 B per peer: X25519(static private key, that peer's public key)
+  uint32_t mask;           // capacity - 1; bucket = hs_peer_bucket(first two words of the key) & mask
+  uint32_t count;
+};
+
+__host__ __device__ inline uint32_t hs_peer_bucket(uint32_t w0, uint32_t w1) { return rx_mix(w0 ^ rx_mix(w1)); }
+
 struct HsState {
-  DevBuf d_key;    // the mac1 key, 32 B (fixed address)
+  DevBuf d_key;    // [0, 32) the mac1 key, [32, 64) H(H0 || static public key) (wg_hs_static_set) (fixed address)
   DevBuf d_priv;   // the static private key, 32 B (fixed address; wg_hs_static_set, wg_x25519.hip)
-  DevBuf d_stage;  // wg_hs_key_set: descriptor, "mac1----" || public key, status; wg_hs_static_set: [128, 196)
+  DevBuf d_stage;  // wg_hs_key_set: descriptor, "mac1----" || public key, status; wg_hs_static_set: [128, 196), [256, 356)
   DevBuf d_part;   // per range of 256 list positions: {valid, init, resp, rejected}, then their exclusive prefixes
+  // wg_hs_open.hip: the peer table's header (fixed address), the table of a context without peers, the current
+  // table, the publics behind 32 B that hold the private key while the secrets are computed, the secrets, the
+  // k_x25519 descriptors and statuses that compute them; per record the open's results, per range its counts
+  DevBuf d_phdr, d_pempty, d_pslots, d_pin, d_psec, d_pdesc, d_ores, d_opart;
+  uint32_t n_peers = 0;
   bool has_key = false;
   bool has_priv = false;
   hipEvent_t ev = nullptr;  // last use of the scratch, and its stream
@@ -51,17 +66,23 @@ int hs_get(wg_ctx* c, HsState** out) {
   if (!c->hs) {
     auto t = std::make_unique<HsState>();
     int rc;
-    if ((rc = t->d_key.ensure(32)) != WG_OK || (rc = t->d_priv.ensure(32)) != WG_OK ||
-        (rc = t->d_stage.ensure(256)) != WG_OK) {
-      for (DevBuf* b : {&t->d_key, &t->d_priv, &t->d_stage}) b->release();
+    if ((rc = t->d_key.ensure(64)) != WG_OK || (rc = t->d_priv.ensure(32)) != WG_OK ||
+        (rc = t->d_stage.ensure(512)) != WG_OK || (rc = t->d_phdr.ensure(sizeof(HsPeerHdr))) != WG_OK ||
+        (rc = t->d_pempty.ensure(16 * sizeof(uint32_t))) != WG_OK) {
+      for (DevBuf* b : {&t->d_key, &t->d_priv, &t->d_stage, &t->d_phdr, &t->d_pempty}) b->release();
       return rc;
     }
+    HsPeerHdr H{};  // no peers
+    H.slots = (const uint32_t*)t->d_pempty.p;
+    H.mask = 15u;
     hipError_t e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMemsetAsync(t->d_key.p, 0, 32, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_key.p, 0, 64, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(t->d_priv.p, 0, 32, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_pempty.p, 0, 16 * sizeof(uint32_t), c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(t->d_phdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
-      for (DevBuf* b : {&t->d_key, &t->d_priv, &t->d_stage}) b->release();
+      for (DevBuf* b : {&t->d_key, &t->d_priv, &t->d_stage, &t->d_phdr, &t->d_pempty}) b->release();
       if (t->ev) (void)hipEventDestroy(t->ev);
       return fail(WG_EDEVICE, "handshake state: %s", hipGetErrorString(e));
     }
@@ -76,23 +97,39 @@ void hs_free(wg_ctx* c) {
   HsState* t = c->hs;
   if (t->d_key.p) {  // the keys are wiped, like the key table
     (void)hipDeviceSynchronize();
-    (void)hipMemsetAsync(t->d_key.p, 0, 32, c->stream);
+    (void)hipMemsetAsync(t->d_key.p, 0, 64, c->stream);
     if (t->d_priv.p) (void)hipMemsetAsync(t->d_priv.p, 0, 32, c->stream);
+    // the peers' static-static secrets, and what the last open derived from them
+    for (DevBuf* b : {&t->d_psec, &t->d_pin, &t->d_ores})
+      if (b->p) (void)hipMemsetAsync(b->p, 0, b->cap, c->stream);
     (void)hipStreamSynchronize(c->stream);
   }
-  for (DevBuf* b : {&t->d_key, &t->d_priv, &t->d_stage, &t->d_part}) b->release();
+  for (DevBuf* b : {&t->d_key, &t->d_priv, &t->d_stage, &t->d_part, &t->d_phdr, &t->d_pempty, &t->d_pslots, &t->d_pin,
+                    &t->d_psec, &t->d_pdesc, &t->d_ores, &t->d_opart})
+    b->release();
   if (t->ev) (void)hipEventDestroy(t->ev);
   delete t;
   c->hs = nullptr;
 }
 
-bool hs_scratch_fits(const HsState* t, uint32_t n) { return (size_t)std::max(rxp_blocks(n), 1u) * 16 <= t->d_part.cap; }
-// scratch for checks of up to n messages; never on a capturing stream (the caller checks)
-int hs_scratch(HsState* t, uint32_t n) {
-  if (hs_scratch_fits(t, n)) return WG_OK;
-  HIPTRY(hipDeviceSynchronize());  // the scratch is reallocated under earlier calls
-  return t->d_part.ensure((size_t)std::max(rxp_blocks(n), 1u) * 16);
+// open: the scratch of wg_hs_open too (per record 112 B of results, per range its counts)
+bool hs_scratch_fits(const HsState* t, uint32_t n, bool open = false) {
+  const size_t part = (size_t)std::max(rxp_blocks(n), 1u) * 16;
+  return part <= t->d_part.cap && (!open || (part <= t->d_opart.cap && (size_t)std::max(n, 1u) * 112 <= t->d_ores.cap));
 }
+// scratch for checks (and opens) of up to n messages; never on a capturing stream (the caller checks)
+int hs_scratch(HsState* t, uint32_t n, bool open = false) {
+  if (hs_scratch_fits(t, n, open)) return WG_OK;
+  HIPTRY(hipDeviceSynchronize());  // the scratch is reallocated under earlier calls
+  const size_t part = (size_t)std::max(rxp_blocks(n), 1u) * 16;
+  int rc;
+  if ((rc = t->d_part.ensure(part)) != WG_OK || !open) return rc;
+  if (t->d_ores.p && t->d_ores.cap < (size_t)std::max(n, 1u) * 112) HIPTRY(hipMemset(t->d_ores.p, 0, t->d_ores.cap));  // freed: wiped first
+  if ((rc = t->d_opart.ensure(part)) != WG_OK) return rc;
+  return t->d_ores.ensure((size_t)std::max(n, 1u) * 112);
+}
+
+int hs_open_rekey(wg_ctx* c, HsState* t, const uint8_t* static_public);  // wg_hs_open.hip
 
 }  // namespace
 
@@ -422,7 +459,7 @@ int wg_hs_reserve(wg_ctx* c, uint32_t max_messages) {
   HsState* t;
   int rc;
   if ((rc = hs_get(c, &t)) != WG_OK) return rc;
-  return hs_scratch(t, max_messages);
+  return hs_scratch(t, max_messages, true);
 }
 
 int wg_hs_check(wg_ctx* c, const wg_hs_batch* b, void* stream) {

@@ -441,6 +441,7 @@ int wg_hs_static_set(wg_ctx* c, const uint8_t* static_private, uint8_t* static_p
   HIPTRY(hipStreamSynchronize(c->stream));
   t->has_priv = true;
   if ((rc = hs_mac1_key_set(c, t, pub)) != WG_OK) return rc;  // as wg_hs_key_set(public)
+  if ((rc = hs_open_rekey(c, t, pub)) != WG_OK) return rc;    // H(H0 || public), the stored peers' secrets
   if (static_public_out) memcpy(static_public_out, pub, 32);
   return WG_OK;
 }

@@ -39,6 +39,9 @@ WG_AEAD_DTYPE = np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("aad_off", "<u
 WG_B2S_DTYPE = np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("key_off", "<u8"), ("len", "<u4"), ("outlen", "u1"),
                          ("keylen", "u1"), ("_pad", "u1", (2,))])
 WG_HS_RECORD_DTYPE = np.dtype([("index", "<u4"), ("len", "<u4"), ("msg", "u1", (148,)), ("_pad", "<u4")])
+WG_HS_INIT_DTYPE = np.dtype([("index", "<u4"), ("record", "<u4"), ("sender_index", "<u4"), ("peer", "<u4"),
+                             ("remote_ephemeral", "u1", (32,)), ("remote_static", "u1", (32,)), ("hash", "u1", (32,)),
+                             ("chain_key", "u1", (32,))])
 
 
 def pack_b2s_desc(in_off, out_off, key_off, length, outlen, keylen) -> np.ndarray:
@@ -488,6 +491,59 @@ class Engine:
         n_records = hs_summary.data_ptr() + L.WgHsSummary.n_valid.offset if hs_summary is not None else None
         b = L.WgHsDhBatch(records.data_ptr(), n_records, shared.data_ptr(), dh_status.data_ptr(), records.shape[0], 0)
         L.check(self._lib.wg_hs_dh(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    # ---- the initiations' encrypted static (wg_hs_peers_set / wg_hs_open) ---------------------
+    def hs_peers_set(self, publics) -> None:
+        """wg_hs_peers_set: the peers' static public keys (32 n bytes, or a sequence of 32-byte keys) onto the
+        device, with each peer's static-static secret under the key of hs_static_set. A peer is named by its
+        position; two equal keys are refused."""
+        if not isinstance(publics, (bytes, bytearray, memoryview, np.ndarray)):
+            publics = b"".join(bytes(p) for p in publics)
+        pk = np.frombuffer(bytes(publics), np.uint8).copy()
+        if pk.size % 32:
+            raise L.WgError(L.WG_EINVAL, f"{pk.size} bytes of static public keys: not a multiple of 32")
+        L.check(self._lib.wg_hs_peers_set(self.ctx, pk.ctypes.data if pk.size else None, pk.size // 32))
+
+    def hs_open(self, records, hs_summary, shared, dh_status, open_status, inits, open_summary,
+                stream: int | None = None) -> None:
+        """wg_hs_open over torch tensors: records and hs_summary as hs_check() wrote them (hs_summary None: all
+        n records), shared and dh_status as hs_dh() wrote them, open_status int32 [n] (WG_HS_OPEN_*), inits
+        uint8 [n, 144] (wg_hs_init, WG_HS_INIT_DTYPE), open_summary int32 [4] (n_emitted, n_known, n_badauth,
+        n_skipped). Check, dh and open run back to back on one stream."""
+        n_records = hs_summary.data_ptr() + L.WgHsSummary.n_valid.offset if hs_summary is not None else None
+        b = L.WgHsOpenBatch(records.data_ptr(), n_records, shared.data_ptr(), dh_status.data_ptr(),
+                            open_status.data_ptr(), inits.data_ptr(), open_summary.data_ptr(), records.shape[0], 0)
+        L.check(self._lib.wg_hs_open(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def hs_open_host(self, remote_ephemeral, encrypted_static, encrypted_timestamp):
+        """One initiation's fields through hs_dh + hs_open under the key of hs_static_set: returns (WG_HS_OPEN_*
+        status, the wg_hs_init entry as a WG_HS_INIT_DTYPE scalar, or None when nothing was emitted). For the
+        noise mirror and tests; a data path runs the chain over a ring."""
+        import torch
+        if len(remote_ephemeral) != 32 or len(encrypted_static) != 48 or len(encrypted_timestamp) != 28:
+            raise L.WgError(L.WG_EINVAL, "an initiation carries 32 + 48 + 28 bytes")
+        dev = torch.device("cuda", self.device)
+        rec = np.zeros(1, WG_HS_RECORD_DTYPE)
+        rec["len"] = L.WG_HS_INIT_SIZE
+        msg = bytes([1, 0, 0, 0, 0, 0, 0, 0]) + bytes(remote_ephemeral) + bytes(encrypted_static) + bytes(encrypted_timestamp)
+        rec["msg"][0, :len(msg)] = np.frombuffer(msg, np.uint8)
+        d_rec = torch.from_numpy(rec.view(np.uint8).reshape(1, 160)).to(dev)
+        d_sh = torch.zeros(32, dtype=torch.uint8, device=dev)
+        d_ds, d_os = (torch.zeros(1, dtype=torch.int32, device=dev) for _ in range(2))
+        d_init = torch.zeros((1, 144), dtype=torch.uint8, device=dev)
+        d_sum = torch.zeros(4, dtype=torch.int32, device=dev)
+        st = _torch_stream()
+        try:
+            self.hs_dh(d_rec, None, d_sh, d_ds, stream=st)
+            self.hs_open(d_rec, None, d_sh, d_ds, d_os, d_init, d_sum, stream=st)
+            self.sync(st)
+        finally:
+            d_sh.zero_()
+            torch.cuda.synchronize(dev)
+        status = int(d_os.cpu().numpy()[0])
+        if not int(d_sum.cpu().numpy()[0]):
+            return status, None
+        return status, d_init.cpu().numpy().reshape(-1).view(WG_HS_INIT_DTYPE)[0]
 
     def set_receivers(self, receivers) -> None:
         """wg_ctx_set_receivers: device tensor of receiver_index per key slot for

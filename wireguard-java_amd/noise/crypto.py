@@ -32,6 +32,31 @@ class Crypto:
     POLY1305_TAG_SIZE = 16
     ChaChaPoly1305NonceSize = 12
     ChaChaPoly1305Overhead = 16
+    BLAKE2S_BLOCKBYTES = 64
+
+    @staticmethod
+    def HMAC(sum, key, *messages) -> None:
+        """Crypto.HMAC (Crypto.java:39-71): sum = HMAC-BLAKE2s(key, messages...) over the 64-byte block, the two
+        hashes on the device (wg_blake2s_batch). A key longer than a block is hashed first; the digest is
+        cut to sum's size, as digest(sum, 0, sum.length) cuts it."""
+        k = _bytes(key)
+        if len(k) > Crypto.BLAKE2S_BLOCKBYTES:
+            k = BLAKE2s256(k)
+        padded = k + bytes(Crypto.BLAKE2S_BLOCKBYTES - len(k))
+        inner = BLAKE2s256(bytes(b ^ 0x36 for b in padded), *messages)
+        _write(sum, BLAKE2s256(bytes(b ^ 0x5C for b in padded), inner)[:_size(sum)])
+
+    @staticmethod
+    def deriveKey(salt, IKM, n: int = 1) -> bytes:
+        """Crypto.deriveKey (Crypto.java:74-99): T(n) of HKDF(salt, IKM) with empty info."""
+        if n < 1:
+            raise IndexError("n")  # T[n - 1] of an empty array
+        prk = bytearray(32)
+        Crypto.HMAC(prk, salt, IKM)
+        t = bytearray(32)
+        for i in range(1, n + 1):
+            Crypto.HMAC(t, prk, bytes(t) if i > 1 else b"", b"", bytes([i]))
+        return bytes(t)
 
 
 def _bytes(seg) -> bytes:

@@ -1,4 +1,5 @@
-"""ax.xz.wireguard.noise.handshake.SymmetricKeypair mirror — the drop-in boundary.
+"""ax.xz.wireguard.noise.handshake mirror: SymmetricKeypair, the drop-in boundary, and
+Handshakes.decryptRemoteStatic, the responder's first phase on the device.
 
 Keeps the reference API (SymmetricKeypair.java:20-94): cipher(src, dst) -> counter,
 decipher(counter, src, dst) raising BadPaddingException (AEADBadTagException),
@@ -15,6 +16,28 @@ import numpy as np
 from .. import _lib as L
 from ..engine import Engine, default_engine, desc_as_int64, pack_desc
 from .crypto import AEADBadTagException, IllegalStateException, _bytes, _size, _write
+from .keys import NoisePrivateKey, NoisePublicKey
+
+
+class Handshakes:
+    """Handshakes.java: the responder's first phase, on the device."""
+
+    @staticmethod
+    def decryptRemoteStatic(localKeypair: NoisePrivateKey, remoteEphemeral: NoisePublicKey, encryptedStatic,
+                            encryptedTimestamp, engine: Engine | None = None) -> NoisePublicKey:
+        """Handshakes.decryptRemoteStatic (Handshakes.java:47-50, 201-237): the initiator's static public key,
+        or AEADBadTagException (a BadPaddingException) when encryptedStatic does not verify. Like the
+        reference it returns the key whether or not a peer holds it, and never opens encryptedTimestamp.
+        One record through wg_hs_dh + wg_hs_open; localKeypair becomes the engine's static key
+        (hs_static_set), as a responder has one."""
+        eng = engine or default_engine()
+        eng.hs_static_set(localKeypair.data())
+        status, init = eng.hs_open_host(remoteEphemeral.data(), _bytes(encryptedStatic), _bytes(encryptedTimestamp))
+        if status == L.WG_HS_OPEN_BADAUTH:
+            raise AEADBadTagException("Tag mismatch")
+        if init is None:
+            raise L.WgError(L.WG_EINVAL, f"wg_hs_open status {status}")
+        return NoisePublicKey(init["remote_static"].tobytes())
 
 
 class SymmetricKeypair:
