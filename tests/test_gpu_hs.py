@@ -12,7 +12,7 @@ from wgtest import noise, splitmix_np, wg
 
 pytestmark = pytest.mark.gpu
 
-R = 256  # kRxRange: list positions per workgroup of the check / emit launches
+R = 256  # kRankRange of wg_plan.hip: list positions per workgroup of the check / emit launches
 GUARD = 0x7E7E7E7E
 FILL = 0x5A
 PUB = bytes(splitmix_np(0x45, 32))

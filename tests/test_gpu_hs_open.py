@@ -183,6 +183,55 @@ def test_plan_check_dh_open_on_one_stream(rig, n_list):
         eng.close()
 
 
+def test_opens_on_two_streams(rig):
+    """Six opens of two rings issued back to back on two streams, alternating, with no synchronisation between
+    them: they share the scratch (with each other and with wg_hs_check), the library chains them, and each equals
+    what its ring's chain gave on one stream, which compare_open has checked against the model. Ring A lists 300
+    handshake datagrams (two ranges of 256, the second part-filled), ring B 70 (one part-filled range, two waves):
+    calls of different size take the scratch in turn."""
+    torch, dev = rig.torch, rig.dev
+    eng, rig2 = _engine(rig)
+    try:
+        pub = eng.hs_static_set(STATIC)
+        peers = _peers()
+        eng.hs_peers_set(peers)
+        rng = np.random.default_rng(5800)
+        chains = []
+        for n_list in (300, 70):
+            ring, off, lens = _open_ring(rng, n_list, STATIC)
+            ch = _OpenChain(rig2, len(off) + 5, len(ring) + 64)
+            ch.load(ring, off, lens)
+            ch.run()
+            st, inits = ch.compare_open(pub, STATIC, peers)
+            assert {OM.OPEN_OK, OM.OPEN_NEWPEER, OM.OPEN_BADAUTH} <= set(st) and len(inits) > 0
+            want = tuple(t.cpu().numpy().tobytes() for t in (ch.o_st, ch.o_init, ch.o_sum))
+            chains.append((ch, want))
+        outs = []
+        for k in range(6):  # every call's own outputs, with the guards compare_open's expectation carries
+            n = chains[k % 2][0].n
+            outs.append((torch.full((n + 4,), GUARD, dtype=torch.int32, device=dev),
+                         torch.full((n + 1, 144), 0x7E, dtype=torch.uint8, device=dev),
+                         torch.full((8,), GUARD, dtype=torch.int32, device=dev)))
+        streams = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
+        torch.cuda.synchronize()
+        for k in range(6):
+            ch, n = chains[k % 2][0], chains[k % 2][0].n
+            o_st, o_init, o_sum = outs[k]
+            eng.hs_open(ch.d_rec[:n], ch.d_sum[:4], ch.d_shared[:n], ch.d_dh[:n], o_st[:n], o_init[:n], o_sum[:4],
+                        stream=streams[k % 2].cuda_stream)
+        torch.cuda.synchronize()
+        for k, (o_st, o_init, o_sum) in enumerate(outs):
+            n, want = chains[k % 2][0].n, chains[k % 2][1]
+            got = tuple(t.cpu().numpy().tobytes() for t in (o_st, o_init, o_sum))
+            assert got[0] == want[0], ("status", k)
+            assert got[1] == want[1], ("entries", k)
+            assert got[2] == want[2], ("summary", k)
+            assert (o_st.cpu().numpy()[n:] == GUARD).all() and (o_sum.cpu().numpy()[4:] == GUARD).all()
+            assert (o_init.cpu().numpy()[int(o_sum[0]):] == 0x7E).all()  # behind the n_emitted entries
+    finally:
+        eng.close()
+
+
 # ---- the peer table ------------------------------------------------------------------------------------------------
 def _direct(rig2, msgs, private, peers):
     """Records made by hand through wg_hs_dh + wg_hs_open (n_records = NULL), compared whole with the models.

@@ -13,7 +13,7 @@ from wgtest import oracle, splitmix_np, wg
 pytestmark = pytest.mark.gpu
 
 KEY_SLOTS = 1024
-R = 256  # kRxRange of wg_rxplan.hip: packets per workgroup of the classify / emit launches
+R = 256  # kRankRange of wg_plan.hip: packets per workgroup of the classify / emit launches
 SCAN_CHUNK = 256  # ranges the scan launch takes per trip: more than R * SCAN_CHUNK packets take a second trip
 GUARD = 0x7E7E7E7E
 FILL = 0x5A

@@ -59,8 +59,12 @@ int fail(int code, const char* fmt, ...) {
                                       __FILE__, __LINE__);                                       \
   } while (0)
 
-// grow-only device buffer
+// grow-only device buffer, freed with its owner (under the owner's DeviceGuard)
 struct DevBuf {
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   void* p = nullptr;
   size_t cap = 0;
   // a histogram workspace used by k_lpt_one: its two counter sets (zeroed = both are zero or hold this
@@ -805,6 +809,7 @@ int launch_after_seal(wg_ctx* c, const wg_batch* sb, const wg_batch* ob, hipStre
 
 }  // namespace
 
+#include "wg_plan.hip"
 #include "wg_rx.hip"
 #include "wg_tx.hip"
 #include "wg_rxplan.hip"
@@ -945,15 +950,8 @@ int wg_ctx_destroy(wg_ctx* c) {
     (void)hipEventDestroy(e.first);
     (void)hipEventDestroy(e.second);
   }
-  for (DevBuf* b : {&c->plan_nb, &c->plan_prefix, &c->plan_tiles, &c->plan_ntiles, &c->plan_tmp, &c->lpt_hist,
-                    &c->lpt_order, &c->lpt_hist2, &c->lpt_order2, &c->lpt_nlong, &c->h_desc, &c->h_in, &c->h_out, &c->h_aad, &c->h_status,
-                    &c->h_keys})
-    b->release();
-  for (auto& w : c->stream_ws) {
-    w->hist.release();
-    w->order.release();
+  for (auto& w : c->stream_ws)
     if (w->ev) (void)hipEventDestroy(w->ev);
-  }
   if (c->stream) (void)hipStreamDestroy(c->stream);
   if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
   if (c->copy_out_stream) (void)hipStreamDestroy(c->copy_out_stream);

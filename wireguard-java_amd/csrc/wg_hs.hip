@@ -22,15 +22,14 @@
 // instead of 64; the bytes behind the range are masked to zero.
 //
 // Ranks. records[0 .. n_valid) is the stable compaction of the accepted messages; it takes the three
-// launches of wg_rxplan.hip's ranks (check, scan, emit), with k_rx_scan called as it is: the check
+// launches of wg_plan.hip's rank_launch (check, scan, emit), with k_rx_scan called as it is: the check
 // launch leaves one 16-B record {valid, initiations, responses, rejected} per range of 256 list
 // positions, the scan turns them into exclusive prefixes and writes their totals as the summary, the
 // emit launch places. The list's length is read on the device (it is the plan's n_host, written earlier
 // on the same stream): the grid is sized from n, and a workgroup past the list writes a zero record and
 // exits. Every scratch word is written by the first launch of a call before a later one reads it and
 // nothing about a call lives on the host, so a captured plan + check replays. The mac1 key sits at a
-// fixed device address (the TxRouteHdr pattern of wg_tx.hip): wg_hs_key_set between replays needs no
-// re-capture.
+// fixed device address (wg_plan.hip, fixed headers): wg_hs_key_set between replays needs no re-capture.
 #pragma once
 
 namespace {
@@ -43,7 +42,7 @@ struct HsPeerHdr {  // at a fixed device address; wg_hs_peers_set rewrites it (a
   uint32_t count;
 };
 
-__host__ __device__ inline uint32_t hs_peer_bucket(uint32_t w0, uint32_t w1) { return rx_mix(w0 ^ rx_mix(w1)); }
+__host__ __device__ inline uint32_t hs_peer_bucket(uint32_t w0, uint32_t w1) { return mix32(w0 ^ mix32(w1)); }
 
 struct HsState {
   DevBuf d_key;    // [0, 32) the mac1 key, [32, 64) H(H0 || static public key) (wg_hs_static_set) (fixed address)
@@ -57,9 +56,11 @@ struct HsState {
   uint32_t n_peers = 0;
   bool has_key = false;
   bool has_priv = false;
-  hipEvent_t ev = nullptr;  // last use of the scratch, and its stream
-  hipStream_t ev_stream = (hipStream_t)-1;
+  StreamOrder order;  // last check / open: they share the scratch
 };
+
+const PlanWords kHsCheckWords{"handshake check", "datagrams", "wg_hs_reserve"};
+const PlanWords kHsOpenWords{"handshake open", "records", "wg_hs_reserve"};
 
 // The handshake state, allocated at the first wg_hs_* call. Caller holds c->mu.
 int hs_get(wg_ctx* c, HsState** out) {
@@ -68,24 +69,18 @@ int hs_get(wg_ctx* c, HsState** out) {
     int rc;
     if ((rc = t->d_key.ensure(64)) != WG_OK || (rc = t->d_priv.ensure(32)) != WG_OK ||
         (rc = t->d_stage.ensure(512)) != WG_OK || (rc = t->d_phdr.ensure(sizeof(HsPeerHdr))) != WG_OK ||
-        (rc = t->d_pempty.ensure(16 * sizeof(uint32_t))) != WG_OK) {
-      for (DevBuf* b : {&t->d_key, &t->d_priv, &t->d_stage, &t->d_phdr, &t->d_pempty}) b->release();
+        (rc = t->d_pempty.ensure(16 * sizeof(uint32_t))) != WG_OK)
       return rc;
-    }
     HsPeerHdr H{};  // no peers
     H.slots = (const uint32_t*)t->d_pempty.p;
     H.mask = 15u;
-    hipError_t e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
+    hipError_t e = t->order.create();
     if (e == hipSuccess) e = hipMemsetAsync(t->d_key.p, 0, 64, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(t->d_priv.p, 0, 32, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(t->d_pempty.p, 0, 16 * sizeof(uint32_t), c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(t->d_phdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-      for (DevBuf* b : {&t->d_key, &t->d_priv, &t->d_stage, &t->d_phdr, &t->d_pempty}) b->release();
-      if (t->ev) (void)hipEventDestroy(t->ev);
-      return fail(WG_EDEVICE, "handshake state: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(WG_EDEVICE, "handshake state: %s", hipGetErrorString(e));
     c->hs = t.release();
   }
   *out = c->hs;
@@ -104,29 +99,27 @@ void hs_free(wg_ctx* c) {
       if (b->p) (void)hipMemsetAsync(b->p, 0, b->cap, c->stream);
     (void)hipStreamSynchronize(c->stream);
   }
-  for (DevBuf* b : {&t->d_key, &t->d_priv, &t->d_stage, &t->d_part, &t->d_phdr, &t->d_pempty, &t->d_pslots, &t->d_pin,
-                    &t->d_psec, &t->d_pdesc, &t->d_ores, &t->d_opart})
-    b->release();
-  if (t->ev) (void)hipEventDestroy(t->ev);
   delete t;
   c->hs = nullptr;
 }
 
 // open: the scratch of wg_hs_open too (per record 112 B of results, per range its counts)
-bool hs_scratch_fits(const HsState* t, uint32_t n, bool open = false) {
-  const size_t part = (size_t)std::max(rxp_blocks(n), 1u) * 16;
+bool hs_scratch_fits(const HsState* t, uint32_t n, bool open) {
+  const size_t part = (size_t)std::max(rank_blocks(n), 1u) * 16;
   return part <= t->d_part.cap && (!open || (part <= t->d_opart.cap && (size_t)std::max(n, 1u) * 112 <= t->d_ores.cap));
 }
-// scratch for checks (and opens) of up to n messages; never on a capturing stream (the caller checks)
-int hs_scratch(HsState* t, uint32_t n, bool open = false) {
-  if (hs_scratch_fits(t, n, open)) return WG_OK;
-  HIPTRY(hipDeviceSynchronize());  // the scratch is reallocated under earlier calls
-  const size_t part = (size_t)std::max(rxp_blocks(n), 1u) * 16;
+// ... and its growth (plan_reserve), for checks (and opens) of up to n messages
+int hs_scratch_grow(HsState* t, uint32_t n, bool open) {
+  const size_t part = (size_t)std::max(rank_blocks(n), 1u) * 16;
   int rc;
   if ((rc = t->d_part.ensure(part)) != WG_OK || !open) return rc;
   if (t->d_ores.p && t->d_ores.cap < (size_t)std::max(n, 1u) * 112) HIPTRY(hipMemset(t->d_ores.p, 0, t->d_ores.cap));  // freed: wiped first
   if ((rc = t->d_opart.ensure(part)) != WG_OK) return rc;
   return t->d_ores.ensure((size_t)std::max(n, 1u) * 112);
+}
+
+int hs_begin(HsState* t, hipStream_t s, bool capturing, uint32_t n, bool open, const PlanWords& w) {
+  return plan_begin(t->order, s, capturing, hs_scratch_fits(t, n, open), [&] { return hs_scratch_grow(t, n, open); }, w, n);
 }
 
 int hs_open_rekey(wg_ctx* c, HsState* t, const uint8_t* static_public);  // wg_hs_open.hip
@@ -232,10 +225,8 @@ __device__ __forceinline__ void b2s_load(const uint8_t* p, uint32_t avail, uint3
   }
 }
 
-// h = the BLAKE2s state after msg[0 .. len) under key[0 .. keylen) for a digest of outlen bytes: the
-// digest is the first outlen bytes of h, little-endian.
-__device__ __forceinline__ void b2s_hash(const uint8_t* msg, uint32_t len, const uint8_t* key, uint32_t keylen,
-                                         uint32_t outlen, uint32_t h[8]) {
+// h = the initial state for a digest of outlen bytes under a key of keylen bytes (RFC 7693 2.5, 3.3)
+__device__ __forceinline__ void b2s_init(uint32_t h[8], uint32_t outlen, uint32_t keylen) {
   h[0] = 0x6A09E667u ^ (outlen | (keylen << 8) | 0x01010000u);
   h[1] = 0xBB67AE85u;
   h[2] = 0x3C6EF372u;
@@ -244,6 +235,13 @@ __device__ __forceinline__ void b2s_hash(const uint8_t* msg, uint32_t len, const
   h[5] = 0x9B05688Cu;
   h[6] = 0x1F83D9ABu;
   h[7] = 0x5BE0CD19u;
+}
+
+// h = the BLAKE2s state after msg[0 .. len) under key[0 .. keylen) for a digest of outlen bytes: the
+// digest is the first outlen bytes of h, little-endian.
+__device__ __forceinline__ void b2s_hash(const uint8_t* msg, uint32_t len, const uint8_t* key, uint32_t keylen,
+                                         uint32_t outlen, uint32_t h[8]) {
+  b2s_init(h, outlen, keylen);
   const uint32_t kb = keylen ? 1u : 0u;  // the key block; it is the last block of a keyed empty message
   const uint32_t mb = len ? (len >> 6) + ((len & 63u) ? 1u : 0u) : 1u - kb;
   const uint32_t nb = kb + mb;
@@ -304,11 +302,11 @@ __device__ __forceinline__ uint32_t hs_list_len(const HsParams& P) {
 __global__ void __launch_bounds__(256) k_hs_check(HsParams P) {
   __shared__ uint32_t s_cnt[4][4];
   const uint32_t nl = hs_list_len(P);
-  if (blockIdx.x * kRxRange >= nl) {  // past the list (workgroup-uniform): a zero record for the scan
+  if (blockIdx.x * kRankRange >= nl) {  // past the list (workgroup-uniform): a zero record for the scan
     if (threadIdx.x == 0) P.part[blockIdx.x] = make_uint4(0u, 0u, 0u, 0u);
     return;
   }
-  const uint32_t k = blockIdx.x * kRxRange + threadIdx.x;
+  const uint32_t k = blockIdx.x * kRankRange + threadIdx.x;
   const bool in = k < nl;
   uint32_t st = WG_HS_BADLEN, t = 0;
   if (in) {
@@ -356,8 +354,8 @@ __global__ void __launch_bounds__(256) k_hs_check(HsParams P) {
 __global__ void __launch_bounds__(256) k_hs_emit(HsParams P) {
   __shared__ uint32_t s_cnt[4];
   const uint32_t nl = hs_list_len(P);
-  if (blockIdx.x * kRxRange >= nl) return;  // (workgroup-uniform)
-  const uint32_t k = blockIdx.x * kRxRange + threadIdx.x;
+  if (blockIdx.x * kRankRange >= nl) return;  // (workgroup-uniform)
+  const uint32_t k = blockIdx.x * kRankRange + threadIdx.x;
   const bool ok = k < nl && P.hs_status[k] == WG_HS_OK;
   const uint4 pre = P.part[blockIdx.x];
   uint32_t r, total;
@@ -397,7 +395,7 @@ int b2s_launch(const wg_b2s_desc* desc, uint32_t n, const uint8_t* in, uint64_t 
   P.out_size = out_size;
   P.status = status;
   P.n = n;
-  hipLaunchKernelGGL(wghs::k_b2s, dim3(rxp_blocks(n)), dim3(256), 0, s, P);
+  hipLaunchKernelGGL(wghs::k_b2s, dim3(rank_blocks(n)), dim3(256), 0, s, P);
   const hipError_t le = hipGetLastError();
   if (le != hipSuccess) return fail(WG_EDEVICE, "k_b2s launch: %s", hipGetErrorString(le));
   return WG_OK;
@@ -459,7 +457,7 @@ int wg_hs_reserve(wg_ctx* c, uint32_t max_messages) {
   HsState* t;
   int rc;
   if ((rc = hs_get(c, &t)) != WG_OK) return rc;
-  return hs_scratch(t, max_messages, true);
+  return plan_reserve(hs_scratch_fits(t, max_messages, true), [&] { return hs_scratch_grow(t, max_messages, true); });
 }
 
 int wg_hs_check(wg_ctx* c, const wg_hs_batch* b, void* stream) {
@@ -474,7 +472,7 @@ int wg_hs_check(wg_ctx* c, const wg_hs_batch* b, void* stream) {
   DeviceGuard g(c->device);
   if (!c->hs || !c->hs->has_key) return fail(WG_ENOKEY, "wg_hs_check before any wg_hs_key_set");
   HsState* t = c->hs;
-  const bool capturing = tx_capturing(s);
+  const bool capturing = stream_capturing(s);
   const uint32_t n = b->n;
   if (n == 0) {
     HIPTRY(hipMemsetAsync(b->summary, 0, sizeof(wg_hs_summary), s));
@@ -484,13 +482,7 @@ int wg_hs_check(wg_ctx* c, const wg_hs_batch* b, void* stream) {
   if (!b->hs_status || (((uintptr_t)b->hs_status) & 3u) || !b->records || (((uintptr_t)b->records) & 15u))
     return fail(WG_EINVAL, "status / record output must be non-NULL and aligned (4 / 16 bytes)");
   int rc;
-  if (capturing) {
-    if (!hs_scratch_fits(t, n))
-      return fail(WG_EINVAL, "handshake check of %u datagrams on a capturing stream needs more scratch: call wg_hs_reserve(%u) first", n, n);
-  } else {
-    if ((rc = hs_scratch(t, n)) != WG_OK) return rc;
-    if (t->ev_stream != s && t->ev_stream != (hipStream_t)-1) HIPTRY(hipStreamWaitEvent(s, t->ev, 0));
-  }
+  if ((rc = hs_begin(t, s, capturing, n, false, kHsCheckWords)) != WG_OK) return rc;
   wghs::HsParams P{};
   P.wire = b->wire;
   P.wire_size = b->wire_size;
@@ -503,17 +495,8 @@ int wg_hs_check(wg_ctx* c, const wg_hs_batch* b, void* stream) {
   P.key = (const uint8_t*)t->d_key.p;
   P.part = (uint4*)t->d_part.p;
   P.n = n;
-  const uint32_t nb = rxp_blocks(n);
-  hipLaunchKernelGGL(wghs::k_hs_check, dim3(nb), dim3(256), 0, s, P);
-  hipLaunchKernelGGL(wgrp::k_rx_scan, dim3(1), dim3(256), 0, s, P.part, nb, (uint2*)b->summary);
-  hipLaunchKernelGGL(wghs::k_hs_emit, dim3(nb), dim3(256), 0, s, P);
-  const hipError_t le = hipGetLastError();
-  if (le != hipSuccess) return fail(WG_EDEVICE, "handshake check kernels: %s", hipGetErrorString(le));
-  if (!capturing) {
-    HIPTRY(hipEventRecord(t->ev, s));
-    t->ev_stream = s;
-  }
-  return WG_OK;
+  rank_launch(wghs::k_hs_check, wghs::k_hs_emit, P, b->summary, s);
+  return plan_end(t->order, s, capturing, kHsCheckWords);
 }
 
 }  // extern "C"

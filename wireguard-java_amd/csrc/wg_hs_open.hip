@@ -40,9 +40,8 @@
 // Peers. wg_hs_peers_set keeps the peers' static public keys on the device, each peer's X25519(S_priv, peer)
 // beside them (one k_x25519 launch), and an open-addressing table over them in wg_rx_sessions_set's manner:
 // capacity = the smallest power of two >= max(16, 4 n), 4-byte entries (peer + 1; 0: empty), bucket =
-// rx_mix(w0 ^ rx_mix(w1)) & mask over the key's first two words, linear probing, a hit confirmed on all 32
-// bytes. Its header sits at a fixed device address (the TxRouteHdr pattern): a captured open reads it when it
-// runs.
+// mix32(w0 ^ mix32(w1)) & mask over the key's first two words, linear probing, a hit confirmed on all 32
+// bytes. Its header sits at a fixed device address (wg_plan.hip, fixed headers).
 //
 // Ranks. inits[0 .. n_emitted) is the stable compaction of the OK and NEWPEER records, in the three launches
 // of wg_hs_check: k_hs_open leaves the lane's results in scratch and one 16-B record {emitted, known, badauth,
@@ -77,22 +76,8 @@ struct OpenParams {
   uint32_t n;
 };
 
-__device__ __forceinline__ uint32_t open_len(const OpenParams& P) {
-  if (!P.n_records) return P.n;
-  const uint32_t nr = *P.n_records;
-  return nr < P.n ? nr : P.n;
-}
+__device__ __forceinline__ uint32_t open_len(const OpenParams& P) { return wgrp::dev_count(P.n_records, P.n); }
 
-__device__ __forceinline__ void b2s_iv256(uint32_t h[8]) {  // unkeyed, 32-byte digest
-  h[0] = 0x6A09E667u ^ 0x01010020u;
-  h[1] = 0xBB67AE85u;
-  h[2] = 0x3C6EF372u;
-  h[3] = 0xA54FF53Au;
-  h[4] = 0x510E527Fu;
-  h[5] = 0x9B05688Cu;
-  h[6] = 0x1F83D9ABu;
-  h[7] = 0x5BE0CD19u;
-}
 __device__ __forceinline__ void set8(uint32_t d[8], const uint32_t s[8]) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) d[j] = s[j];
@@ -164,11 +149,11 @@ __device__ __forceinline__ uint32_t open_static(const uint32_t key[8], const uin
 __global__ void __launch_bounds__(256) k_hs_open(OpenParams P) {
   __shared__ uint32_t s_cnt[4][4];
   const uint32_t nl = open_len(P);
-  if (blockIdx.x * kRxRange >= nl) {  // past the records (workgroup-uniform): a zero record for the scan
+  if (blockIdx.x * kRankRange >= nl) {  // past the records (workgroup-uniform): a zero record for the scan
     if (threadIdx.x == 0) P.part[blockIdx.x] = make_uint4(0u, 0u, 0u, 0u);
     return;
   }
-  const uint32_t k = blockIdx.x * kRxRange + threadIdx.x;
+  const uint32_t k = blockIdx.x * kRankRange + threadIdx.x;
   const bool in = k < nl;
   uint32_t st_out = WG_HS_OPEN_BADDESC;
   if ((k & ~63u) < nl) {  // (wave-uniform: a wave wholly past the records goes straight to the counts)
@@ -202,7 +187,7 @@ __global__ void __launch_bounds__(256) k_hs_open(OpenParams P) {
           const uint4* q = (const uint4*)P.hs0;
           put8(m, q[0], q[1]);
           put8(m + 8, rec[1], rec[2]);
-          b2s_iv256(st);
+          wghs::b2s_init(st, 32u, 0u);
           t = 64u; last = true;
           break;
         }
@@ -223,12 +208,12 @@ __global__ void __launch_bounds__(256) k_hs_open(OpenParams P) {
           break;
         case 3: case 11: case 23:  // the expand's key blocks, PRK ^ ipad / PRK ^ opad
           pad_block(m, x, 0x36363636u);
-          b2s_iv256(st);
+          wghs::b2s_init(st, 32u, 0u);
           t = 64u; last = false;
           break;
         case 4: case 12: case 24:
           pad_block(m, x, 0x5C5C5C5Cu);
-          b2s_iv256(st);
+          wghs::b2s_init(st, 32u, 0u);
           t = 64u; last = false;
           break;
         case 5: case 13: case 25:  // T1 = HMAC(PRK, 0x01): inner
@@ -244,12 +229,12 @@ __global__ void __launch_bounds__(256) k_hs_open(OpenParams P) {
           break;
         case 7: case 19:  // the next extract's key blocks, ck ^ ipad / ck ^ opad
           pad_block(m, ck, 0x36363636u);
-          b2s_iv256(st);
+          wghs::b2s_init(st, 32u, 0u);
           t = 64u; last = false;
           break;
         case 8: case 20:
           pad_block(m, ck, 0x5C5C5C5Cu);
-          b2s_iv256(st);
+          wghs::b2s_init(st, 32u, 0u);
           t = 64u; last = false;
           break;
         case 9: {  // KDF(ck, ss): the extract's inner hash
@@ -282,7 +267,7 @@ __global__ void __launch_bounds__(256) k_hs_open(OpenParams P) {
           any_known = __ballot(peer != 0u) != 0ull;
           set8(m, hh);
           set8(m + 8, es);
-          b2s_iv256(st);
+          wghs::b2s_init(st, 32u, 0u);
           t = 64u; last = false;
           break;
         }
@@ -312,7 +297,7 @@ __global__ void __launch_bounds__(256) k_hs_open(OpenParams P) {
           const uint4 a = rec[6], b = rec[7];
           set8(m, hh);
           m[8] = a.x; m[9] = a.y; m[10] = a.z; m[11] = a.w; m[12] = b.x; m[13] = b.y; m[14] = b.z; m[15] = 0u;
-          b2s_iv256(st);
+          wghs::b2s_init(st, 32u, 0u);
           t = 60u; last = true;
           break;
         }
@@ -354,8 +339,8 @@ __global__ void __launch_bounds__(256) k_hs_open(OpenParams P) {
 __global__ void __launch_bounds__(256) k_hs_open_emit(OpenParams P) {
   __shared__ uint32_t s_cnt[4];
   const uint32_t nl = open_len(P);
-  if (blockIdx.x * kRxRange >= nl) return;  // (workgroup-uniform)
-  const uint32_t k = blockIdx.x * kRxRange + threadIdx.x;
+  if (blockIdx.x * kRankRange >= nl) return;  // (workgroup-uniform)
+  const uint32_t k = blockIdx.x * kRankRange + threadIdx.x;
   bool ok = false;
   if (k < nl) {
     const uint32_t s = P.open_status[k];
@@ -520,15 +505,9 @@ int wg_hs_open(wg_ctx* c, const wg_hs_open_batch* b, void* stream) {
           return fail(WG_EINVAL, "an output of wg_hs_open must not overlap records, shared, dh_status or n_records");
     }
   }
-  const bool capturing = tx_capturing(s);
+  const bool capturing = stream_capturing(s);
   int rc;
-  if (capturing) {
-    if (!hs_scratch_fits(t, n, true))
-      return fail(WG_EINVAL, "handshake open of %u records on a capturing stream needs more scratch: call wg_hs_reserve(%u) first", n, n);
-  } else {
-    if ((rc = hs_scratch(t, n, true)) != WG_OK) return rc;
-    if (t->ev_stream != s && t->ev_stream != (hipStream_t)-1) HIPTRY(hipStreamWaitEvent(s, t->ev, 0));
-  }
+  if ((rc = hs_begin(t, s, capturing, n, true, kHsOpenWords)) != WG_OK) return rc;
   wgho::OpenParams P{};
   P.records = b->records;
   P.n_records = b->n_records;
@@ -541,17 +520,8 @@ int wg_hs_open(wg_ctx* c, const wg_hs_open_batch* b, void* stream) {
   P.res = (uint4*)t->d_ores.p;
   P.part = (uint4*)t->d_opart.p;
   P.n = n;
-  const uint32_t nb = rxp_blocks(n);
-  hipLaunchKernelGGL(wgho::k_hs_open, dim3(nb), dim3(256), 0, s, P);
-  hipLaunchKernelGGL(wgrp::k_rx_scan, dim3(1), dim3(256), 0, s, P.part, nb, (uint2*)b->summary);
-  hipLaunchKernelGGL(wgho::k_hs_open_emit, dim3(nb), dim3(256), 0, s, P);
-  const hipError_t le = hipGetLastError();
-  if (le != hipSuccess) return fail(WG_EDEVICE, "handshake open kernels: %s", hipGetErrorString(le));
-  if (!capturing) {
-    HIPTRY(hipEventRecord(t->ev, s));
-    t->ev_stream = s;
-  }
-  return WG_OK;
+  rank_launch(wgho::k_hs_open, wgho::k_hs_open_emit, P, b->summary, s);
+  return plan_end(t->order, s, capturing, kHsOpenWords);
 }
 
 }  // extern "C"

@@ -392,8 +392,6 @@ void queue_free(wg_queue* q) {
     memset(q->h_key, 0, (size_t)q->cap * 32);  // no session key outlives the queue in pinned memory
     (void)hipHostFree(q->h_key);
   }
-  q->lpt_hist.release();
-  q->lpt_order.release();
   if (q->stream) (void)hipStreamDestroy(q->stream);
 }
 

@@ -77,8 +77,7 @@ struct RxState {
   uint32_t test_skew_ticks = 0;  // s_memrealtime ticks (100 MHz)
   bool test_mutant = false;
   uint64_t checks = 0;      // replay checks queued: the order flag alternates between two words
-  hipEvent_t ev = nullptr;  // last use of the replay scratch, and its stream (stream-ordered reuse)
-  hipStream_t ev_stream = (hipStream_t)-1;
+  StreamOrder order;        // last use of the replay scratch and window state (its event is made by the first mark)
   DevBuf d_tables;          // wgt::RxTables for the fused open (WG_F_RX_FILTER)
   bool tables_valid = false;
 };
@@ -138,13 +137,7 @@ int rx_get(wg_ctx* c, RxState** out) {
 }
 
 void rx_free(wg_ctx* c) {
-  if (!c->rx) return;
-  RxState* r = c->rx;
-  for (DevBuf* b : {&r->d_entries, &r->d_hdr, &r->d_slot_filter, &r->d_top, &r->d_bits, &r->d_newtop, &r->d_tab,
-                    &r->d_pos, &r->d_flag, &r->d_tables})
-    b->release();
-  if (r->ev) (void)hipEventDestroy(r->ev);
-  delete r;
+  delete c->rx;
   c->rx = nullptr;
 }
 
@@ -168,30 +161,20 @@ int rx_tables(wg_ctx* c, const wgt::RxTables** out) {
   return WG_OK;
 }
 
-// Orders stream s behind the last replay check (which may sit on another stream): the window
-// state is read and written by the check's kernels, so a reset or a state read must not overtake
-// them. Caller holds c->mu.
-int rx_after_last_check(RxState* r, hipStream_t s) {
-  if (r->ev && r->ev_stream != s && r->ev_stream != (hipStream_t)-1) HIPTRY(hipStreamWaitEvent(s, r->ev, 0));
-  return WG_OK;
-}
-
 // zero the replay window of key slots [first, first + n) (a new key = a new session), in stream
-// order after every replay check queued before it; later checks (any stream) wait for the reset.
-// Caller holds c->mu.
+// order after every replay check queued before it (the window state is read and written by the
+// check's kernels, so a reset or a state read must not overtake them); later checks (any stream)
+// wait for the reset. Caller holds c->mu.
 int rx_reset_slots(wg_ctx* c, uint32_t first, uint32_t n, hipStream_t s) {
   RxState* r = c->rx;
   if (!r || !r->window || !n) return WG_OK;
   int rc;
-  if ((rc = rx_after_last_check(r, s)) != WG_OK) return rc;
+  if ((rc = r->order.after_last(s)) != WG_OK) return rc;
   HIPTRY(hipMemsetAsync((uint64_t*)r->d_top.p + first, 0, (size_t)n * 8, s));
   HIPTRY(hipMemsetAsync((uint64_t*)r->d_newtop.p + (size_t)first * kTopWays, 0, (size_t)n * 8 * kTopWays, s));
   const size_t words = r->window / 64;
   HIPTRY(hipMemsetAsync((uint64_t*)r->d_bits.p + (size_t)first * words, 0, (size_t)n * words * 8, s));
-  if (!r->ev) HIPTRY(hipEventCreateWithFlags(&r->ev, hipEventDisableTiming));
-  HIPTRY(hipEventRecord(r->ev, s));
-  r->ev_stream = s;
-  return WG_OK;
+  return r->order.mark(s);
 }
 
 }  // namespace
@@ -748,7 +731,7 @@ int wg_replay_state(wg_ctx* c, uint32_t slot, uint64_t* top, uint64_t* bits, uin
   if (bits && words != r->window / 64) return fail(WG_EINVAL, "words must be window_bits / 64");
   DeviceGuard g(c->device);
   int rc;
-  if ((rc = rx_after_last_check(r, c->stream)) != WG_OK) return rc;  // the state after every queued check
+  if ((rc = r->order.after_last(c->stream)) != WG_OK) return rc;  // the state after every queued check
   HIPTRY(hipMemcpyAsync(top, (uint64_t*)r->d_top.p + slot, 8, hipMemcpyDeviceToHost, c->stream));
   if (bits)
     HIPTRY(hipMemcpyAsync(bits, (uint64_t*)r->d_bits.p + (size_t)slot * words, (size_t)words * 8,
@@ -783,8 +766,7 @@ int wg_rx_check(wg_ctx* c, const wg_pkt* desc, uint32_t n, const uint8_t* pt, ui
     int rc;
     // the scratch (table, positions) is shared by the context's replay checks: a check on
     // another stream first waits for the previous one
-    if (!r->ev) HIPTRY(hipEventCreateWithFlags(&r->ev, hipEventDisableTiming));
-    if (r->ev_stream != s && r->ev_stream != (hipStream_t)-1) HIPTRY(hipStreamWaitEvent(s, r->ev, 0));
+    if ((rc = r->order.after_last(s)) != WG_OK) return rc;
     if (n > (1u << 30)) return fail(WG_EINVAL, "replay check of %u packets: at most 2^30 per batch", n);
     uint32_t T = 1024;
     while (T < 2ull * n) T <<= 1;
@@ -830,8 +812,7 @@ int wg_rx_check(wg_ctx* c, const wg_pkt* desc, uint32_t n, const uint8_t* pt, ui
       r->tab_size = 0;  // the table / flag may be left dirty: the next check starts from empty ones
       return fail(WG_EDEVICE, "replay kernels: %s", hipGetErrorString(le));
     }
-    HIPTRY(hipEventRecord(r->ev, s));
-    r->ev_stream = s;
+    if ((rc = r->order.mark(s)) != WG_OK) return rc;
   }
   if (flags & WG_RX_FILTER) {
     P.slot_filter = r->slot_filter_init ? (const uint32_t*)r->d_slot_filter.p : nullptr;

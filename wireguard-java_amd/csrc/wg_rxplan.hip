@@ -16,15 +16,13 @@
 // key slot + 1} (0: empty), bucket = mix(index) & mask with MurmurHash3's 32-bit finaliser as mix (the
 // reference's indices are 0, 1, 2, ..., WireGuard's are random, a test's may be multiples of anything: the
 // finaliser spreads them all), linear probing; at most a quarter full, so a probe sequence is short (a
-// wave walks as long as the longest of its 64) and ends at an empty entry. Its header sits at a fixed device address and names the
-// entries (the TxRouteHdr pattern of wg_tx.hip): a table change may move them, a captured plan reads
-// the header when it runs.
+// wave walks as long as the longest of its 64) and ends at an empty entry. Its header sits at a fixed
+// device address and names the entries (wg_plan.hip, fixed headers).
 //
 // Ranks. The plan needs two stable ranks over the batch (the handshake list, the 64-bit prefix of the
-// packed plaintext offsets) and the deliver one (the item list). Both run the same three launches on
-// the call's stream, with no wait between workgroups (no spin on another block's flag, no assumption
-// about dispatch order):
-//   k_rx_classify / k_rx_merge  one packet per thread, kRxRange = 256 packets per workgroup: the
+// packed plaintext offsets) and the deliver one (the item list). Both are a rank_launch of wg_plan.hip,
+// with no wait between workgroups (no spin on another block's flag, no assumption about dispatch order):
+//   k_rx_classify / k_rx_merge  one packet per thread, kRankRange = 256 packets per workgroup: the
 //                  checks (type byte, probe, header loads; the merge of the two statuses), the
 //                  packet's code to scratch so that none of it is done twice, and the workgroup's
 //                  sums {bytes, count, count} as ONE 16-B record of the partials array.
@@ -42,23 +40,11 @@
 
 namespace {
 
-constexpr uint32_t kRxRange = 256;  // packets per workgroup of the classify / merge / emit / items launches
-
 struct RxSessHdr {  // at a fixed device address; a table change rewrites it (and may move the entries)
   const uint2* entries;  // capacity x {index, key slot + 1 (0: empty)}
-  uint32_t mask;         // capacity - 1; bucket = rx_mix(index) & mask
+  uint32_t mask;         // capacity - 1; bucket = mix32(index) & mask
   uint32_t count;
 };
-
-// MurmurHash3's fmix32
-__host__ __device__ inline uint32_t rx_mix(uint32_t h) {
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
 
 struct RxPlanState {
   DevBuf d_hdr;    // RxSessHdr (fixed address)
@@ -66,11 +52,11 @@ struct RxPlanState {
   DevBuf d_ent;    // the entries of the current table
   DevBuf d_code;   // per packet: {status, key slot, counter lo, counter hi}
   DevBuf d_part;   // per workgroup: {bytes lo, bytes hi, count, count}, then their exclusive prefixes
-  hipEvent_t ev = nullptr;  // last use of the table / scratch, and its stream
-  hipStream_t ev_stream = (hipStream_t)-1;
+  StreamOrder order;  // last plan / deliver / table write
 };
 
-uint32_t rxp_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + kRxRange - 1u) / kRxRange); }
+const PlanWords kRxPlanWords{"receive plan", "packets", "wg_rx_reserve"};
+const PlanWords kRxDeliverWords{"receive deliver", "packets", "wg_rx_reserve"};
 
 void rxp_header(const RxPlanState* t, uint32_t n, bool own, RxSessHdr* H) {
   uint32_t cap = 16;
@@ -86,21 +72,14 @@ int rxp_get(wg_ctx* c, RxPlanState** out) {
   if (!c->rxp) {
     auto t = std::make_unique<RxPlanState>();
     int rc;
-    if ((rc = t->d_hdr.ensure(sizeof(RxSessHdr))) != WG_OK || (rc = t->d_empty.ensure(16 * sizeof(uint2))) != WG_OK) {
-      for (DevBuf* b : {&t->d_hdr, &t->d_empty}) b->release();
-      return rc;
-    }
+    if ((rc = t->d_hdr.ensure(sizeof(RxSessHdr))) != WG_OK || (rc = t->d_empty.ensure(16 * sizeof(uint2))) != WG_OK) return rc;
     RxSessHdr H;
     rxp_header(t.get(), 0, false, &H);
-    hipError_t e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
+    hipError_t e = t->order.create();
     if (e == hipSuccess) e = hipMemsetAsync(t->d_empty.p, 0, 16 * sizeof(uint2), c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(t->d_hdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-      for (DevBuf* b : {&t->d_hdr, &t->d_empty}) b->release();
-      if (t->ev) (void)hipEventDestroy(t->ev);
-      return fail(WG_EDEVICE, "receive plan state: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(WG_EDEVICE, "receive plan state: %s", hipGetErrorString(e));
     c->rxp = t.release();
   }
   *out = c->rxp;
@@ -108,38 +87,20 @@ int rxp_get(wg_ctx* c, RxPlanState** out) {
 }
 
 void rxp_free(wg_ctx* c) {
-  if (!c->rxp) return;
-  RxPlanState* t = c->rxp;
-  for (DevBuf* b : {&t->d_hdr, &t->d_empty, &t->d_ent, &t->d_code, &t->d_part}) b->release();
-  if (t->ev) (void)hipEventDestroy(t->ev);
-  delete t;
+  delete c->rxp;
   c->rxp = nullptr;
 }
 
-// Orders stream s behind the last plan / deliver / table write (which may sit on another stream), and
-// the next one behind what s does now. Caller holds c->mu.
-int rxp_after_last(RxPlanState* t, hipStream_t s) {
-  if (t->ev_stream != s && t->ev_stream != (hipStream_t)-1) HIPTRY(hipStreamWaitEvent(s, t->ev, 0));
-  return WG_OK;
-}
-int rxp_mark(RxPlanState* t, hipStream_t s) {
-  HIPTRY(hipEventRecord(t->ev, s));
-  t->ev_stream = s;
-  return WG_OK;
-}
-
+// scratch for batches of up to n packets: does it fit, and (plan_reserve) its growth
 bool rxp_scratch_fits(const RxPlanState* t, uint32_t n) {
-  return (size_t)std::max(n, 1u) * 16 <= t->d_code.cap && (size_t)std::max(rxp_blocks(n), 1u) * 16 <= t->d_part.cap;
+  return (size_t)std::max(n, 1u) * 16 <= t->d_code.cap && (size_t)std::max(rank_blocks(n), 1u) * 16 <= t->d_part.cap;
 }
-// scratch for batches of up to n packets; never on a capturing stream (the caller checks)
-int rxp_scratch(RxPlanState* t, uint32_t n) {
-  if (rxp_scratch_fits(t, n)) return WG_OK;
-  HIPTRY(hipDeviceSynchronize());  // the scratch is reallocated under earlier calls
-  int rc;
-  if ((rc = t->d_code.ensure((size_t)std::max(n, 1u) * 16)) != WG_OK ||
-      (rc = t->d_part.ensure((size_t)std::max(rxp_blocks(n), 1u) * 16)) != WG_OK)
-    return rc;
-  return WG_OK;
+int rxp_scratch_grow(RxPlanState* t, uint32_t n) {
+  const int rc = t->d_code.ensure((size_t)std::max(n, 1u) * 16);
+  return rc != WG_OK ? rc : t->d_part.ensure((size_t)std::max(rank_blocks(n), 1u) * 16);
+}
+int rxp_begin(RxPlanState* t, hipStream_t s, bool capturing, uint32_t n, const PlanWords& w) {
+  return plan_begin(t->order, s, capturing, rxp_scratch_fits(t, n), [&] { return rxp_scratch_grow(t, n); }, w, n);
 }
 
 }  // namespace
@@ -177,56 +138,11 @@ struct RxDeliverParams {
   uint4* part;
 };
 
-__device__ __forceinline__ uint64_t u64_of(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
-
-__device__ __forceinline__ uint64_t shfl_up64(uint64_t v, uint32_t d) {
-  const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d), hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d);
-  return u64_of(lo, hi);
-}
-
-// Over the 256 threads of the workgroup, in thread order: the flagged threads below me (rank) and in
-// all (total). Every thread must reach the call; `wsum` is 4 words of LDS of this call's own.
-__device__ __forceinline__ void block_rank(bool flag, uint32_t* wsum, uint32_t& rank, uint32_t& total) {
-  const uint64_t m = __ballot(flag);
-  const uint32_t w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63u) == 0) wsum[w] = (uint32_t)__popcll((unsigned long long)m);
-  __syncthreads();
-  rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-  total = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < 4; ++k) {
-    const uint32_t x = wsum[k];
-    rank += k < w ? x : 0u;
-    total += x;
-  }
-}
-
-// The same for a 64-bit value: the sum of v over the threads below me (excl) and over all (total).
-__device__ __forceinline__ void block_scan64(uint64_t v, uint64_t* wsum, uint64_t& excl, uint64_t& total) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  uint64_t inc = v;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint64_t up = shfl_up64(inc, d);
-    if (lane >= d) inc += up;
-  }
-  if (lane == 63u) wsum[w] = inc;
-  __syncthreads();
-  excl = inc - v;
-  total = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < 4; ++k) {
-    const uint64_t x = wsum[k];
-    excl += k < w ? x : 0ull;
-    total += x;
-  }
-}
-
 // key slot + 1 of a receiver index, 0 if the table does not hold it. Two entries of the probe sequence
 // are fetched per round trip (each one 8-B load): a wave walks as long as its longest chain.
 __device__ __forceinline__ uint32_t rx_session(const RxSessHdr& H, uint32_t index) {
   const uint64_t* ent = (const uint64_t*)H.entries;  // {index, key slot + 1} = low, high word
-  uint32_t b = rx_mix(index);
+  uint32_t b = mix32(index);
   for (uint32_t probes = 0; probes <= H.mask; probes += 2u) {  // (a table a quarter full ends the walk long before)
     const uint64_t e0 = ent[b & H.mask], e1 = ent[(b + 1u) & H.mask];
     if (!(uint32_t)(e0 >> 32)) return 0u;
@@ -242,7 +158,7 @@ __device__ __forceinline__ uint32_t rx_session(const RxSessHdr& H, uint32_t inde
 __global__ void __launch_bounds__(256) k_rx_classify(RxPlanParams P) {
   __shared__ uint32_t s_cnt[2][4];
   __shared__ uint64_t s_sum[4];
-  const uint32_t i = blockIdx.x * kRxRange + threadIdx.x;
+  const uint32_t i = blockIdx.x * kRankRange + threadIdx.x;
   const bool in = i < P.n;
   const RxSessHdr H = *P.sessions;
   uint32_t st = WG_PKT_BADHDR, slot = 0, len = 0, c_lo = 0, c_hi = 0;
@@ -290,39 +206,10 @@ __global__ void __launch_bounds__(256) k_rx_classify(RxPlanParams P) {
   if (threadIdx.x == 0) P.part[blockIdx.x] = make_uint4((uint32_t)bytes, (uint32_t)(bytes >> 32), n_ok, n_host);
 }
 
-// Exclusive prefixes of the per-range records, in place, and the totals as the 16-B summary
-// {bytes, count, count} (wg_rx_summary / wg_rx_delivered). One workgroup.
-__global__ void __launch_bounds__(256) k_rx_scan(uint4* part, uint32_t nb, uint2* summary) {
-  __shared__ uint64_t s_sum[4];
-  uint64_t run_bytes = 0;
-  uint32_t run_a = 0, run_b = 0;
-  for (uint32_t b0 = 0; b0 < nb; b0 += 256u) {  // (workgroup-uniform trips)
-    const uint32_t b = b0 + threadIdx.x;
-    const uint4 v = b < nb ? part[b] : make_uint4(0u, 0u, 0u, 0u);
-    // counts of one range are <= 256: their scans run as 64-bit sums of a packed pair
-    uint64_t ex, tot, exc, totc;
-    block_scan64(u64_of(v.x, v.y), s_sum, ex, tot);
-    __syncthreads();  // s_sum is read by every thread before the next scan writes it
-    block_scan64(u64_of(v.z, v.w), s_sum, exc, totc);
-    __syncthreads();
-    if (b < nb) {
-      const uint64_t pb = run_bytes + ex;
-      part[b] = make_uint4((uint32_t)pb, (uint32_t)(pb >> 32), run_a + (uint32_t)exc, run_b + (uint32_t)(exc >> 32));
-    }
-    run_bytes += tot;
-    run_a += (uint32_t)totc;
-    run_b += (uint32_t)(totc >> 32);
-  }
-  if (threadIdx.x == 0) {  // (8-B stores: the summary need not be 16-B aligned)
-    summary[0] = make_uint2((uint32_t)run_bytes, (uint32_t)(run_bytes >> 32));
-    summary[1] = make_uint2(run_a, run_b);
-  }
-}
-
 __global__ void __launch_bounds__(256) k_rx_emit(RxPlanParams P) {
   __shared__ uint32_t s_cnt[2][4];
   __shared__ uint64_t s_sum[4];
-  const uint32_t i = blockIdx.x * kRxRange + threadIdx.x;
+  const uint32_t i = blockIdx.x * kRankRange + threadIdx.x;
   const bool in = i < P.n;
   const uint4 c = in ? P.code[i] : make_uint4(WG_PKT_BADHDR, 0u, 0u, 0u);
   const uint64_t o = in ? P.pkt_off[i] : 0ull;
@@ -357,7 +244,7 @@ __global__ void __launch_bounds__(256) k_rx_emit(RxPlanParams P) {
 __global__ void __launch_bounds__(256) k_rx_merge(RxDeliverParams P) {
   __shared__ uint32_t s_cnt[2][4];
   __shared__ uint64_t s_sum[4];
-  const uint32_t i = blockIdx.x * kRxRange + threadIdx.x;
+  const uint32_t i = blockIdx.x * kRankRange + threadIdx.x;
   const bool in = i < P.n;
   uint32_t st = WG_PKT_BADHDR, len = 0;
   if (in) {
@@ -376,7 +263,7 @@ __global__ void __launch_bounds__(256) k_rx_merge(RxDeliverParams P) {
 
 __global__ void __launch_bounds__(256) k_rx_items(RxDeliverParams P) {
   __shared__ uint32_t s_cnt[4];
-  const uint32_t i = blockIdx.x * kRxRange + threadIdx.x;
+  const uint32_t i = blockIdx.x * kRankRange + threadIdx.x;
   const bool in = i < P.n;
   const bool ok = in && P.final_status[i] == WG_PKT_OK;
   const uint4 pre = P.part[blockIdx.x];
@@ -408,7 +295,7 @@ int wg_rx_sessions_set(wg_ctx* c, const uint32_t* indices, const uint32_t* slots
   std::vector<uint2> ent(n ? (size_t)H.mask + 1 : 0, make_uint2(0u, 0u));
   for (uint32_t k = 0; k < n; ++k) {
     if (slots[k] >= c->key_slots) return fail(WG_ERANGE, "session %u: key slot %u >= %u", k, slots[k], c->key_slots);
-    uint32_t b = rx_mix(indices[k]) & H.mask;
+    uint32_t b = mix32(indices[k]) & H.mask;
     while (ent[b].y) {
       if (ent[b].x == indices[k]) return fail(WG_EINVAL, "session %u: receiver index 0x%08x repeats", k, indices[k]);
       b = (b + 1u) & H.mask;
@@ -427,7 +314,7 @@ int wg_rx_sessions_set(wg_ctx* c, const uint32_t* indices, const uint32_t* slots
     HIPTRY(hipMemcpyAsync(t->d_ent.p, ent.data(), ent.size() * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
   }
   HIPTRY(hipMemcpyAsync(t->d_hdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream));
-  if ((rc = rxp_mark(t, c->stream)) != WG_OK) return rc;
+  if ((rc = t->order.mark(c->stream)) != WG_OK) return rc;
   HIPTRY(hipStreamSynchronize(c->stream));
   return WG_OK;
 }
@@ -439,7 +326,7 @@ int wg_rx_reserve(wg_ctx* c, uint32_t max_packets) {
   RxPlanState* t;
   int rc;
   if ((rc = rxp_get(c, &t)) != WG_OK) return rc;
-  return rxp_scratch(t, max_packets);
+  return plan_reserve(rxp_scratch_fits(t, max_packets), [&] { return rxp_scratch_grow(t, max_packets); });
 }
 
 int wg_rx_plan(wg_ctx* c, const wg_rx_batch* b, void* stream) {
@@ -450,7 +337,7 @@ int wg_rx_plan(wg_ctx* c, const wg_rx_batch* b, void* stream) {
   hipStream_t s = pick_stream(c, stream);
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  const bool capturing = tx_capturing(s);
+  const bool capturing = stream_capturing(s);
   if (capturing && !c->rxp)
     return fail(WG_EINVAL, "receive plan on a capturing stream before any wg_rx_* planning call: call wg_rx_reserve first");
   RxPlanState* t;
@@ -465,13 +352,7 @@ int wg_rx_plan(wg_ctx* c, const wg_rx_batch* b, void* stream) {
   if (!b->desc_out || (((uintptr_t)b->desc_out) & 15u) || !b->rx_status || (((uintptr_t)b->rx_status) & 3u) ||
       !b->host_list || (((uintptr_t)b->host_list) & 3u))
     return fail(WG_EINVAL, "descriptor / status / host list output must be non-NULL and aligned (16 / 4 / 4 bytes)");
-  if (capturing) {
-    if (!rxp_scratch_fits(t, n))
-      return fail(WG_EINVAL, "receive plan of %u packets on a capturing stream needs more scratch: call wg_rx_reserve(%u) first", n, n);
-  } else {
-    if ((rc = rxp_scratch(t, n)) != WG_OK) return rc;
-    if ((rc = rxp_after_last(t, s)) != WG_OK) return rc;
-  }
+  if ((rc = rxp_begin(t, s, capturing, n, kRxPlanWords)) != WG_OK) return rc;
   wgrp::RxPlanParams P{};
   P.wire = b->wire;
   P.wire_size = b->wire_size;
@@ -490,14 +371,8 @@ int wg_rx_plan(wg_ctx* c, const wg_rx_batch* b, void* stream) {
   P.sessions = (const RxSessHdr*)t->d_hdr.p;
   P.code = (uint4*)t->d_code.p;
   P.part = (uint4*)t->d_part.p;
-  const uint32_t nb = rxp_blocks(n);
-  hipLaunchKernelGGL(wgrp::k_rx_classify, dim3(nb), dim3(256), 0, s, P);
-  hipLaunchKernelGGL(wgrp::k_rx_scan, dim3(1), dim3(256), 0, s, P.part, nb, (uint2*)b->summary);
-  hipLaunchKernelGGL(wgrp::k_rx_emit, dim3(nb), dim3(256), 0, s, P);
-  const hipError_t le = hipGetLastError();
-  if (le != hipSuccess) return fail(WG_EDEVICE, "receive plan kernels: %s", hipGetErrorString(le));
-  if (!capturing && (rc = rxp_mark(t, s)) != WG_OK) return rc;
-  return WG_OK;
+  rank_launch(wgrp::k_rx_classify, wgrp::k_rx_emit, P, b->summary, s);
+  return plan_end(t->order, s, capturing, kRxPlanWords);
 }
 
 int wg_rx_deliver(wg_ctx* c, const wg_rx_deliver_batch* b, void* stream) {
@@ -507,7 +382,7 @@ int wg_rx_deliver(wg_ctx* c, const wg_rx_deliver_batch* b, void* stream) {
   hipStream_t s = pick_stream(c, stream);
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  const bool capturing = tx_capturing(s);
+  const bool capturing = stream_capturing(s);
   if (capturing && !c->rxp)
     return fail(WG_EINVAL, "receive deliver on a capturing stream before any wg_rx_* planning call: call wg_rx_reserve first");
   RxPlanState* t;
@@ -524,13 +399,7 @@ int wg_rx_deliver(wg_ctx* c, const wg_rx_deliver_batch* b, void* stream) {
     return fail(WG_EINVAL, "final_status may alias neither plan_status nor open_status");
   if (!b->items || (((uintptr_t)b->items) & 15u) || (((uintptr_t)b->index_out) & 3u))
     return fail(WG_EINVAL, "items must be non-NULL and 16-byte aligned (index_out: 4-byte)");
-  if (capturing) {
-    if (!rxp_scratch_fits(t, n))
-      return fail(WG_EINVAL, "receive deliver of %u packets on a capturing stream needs more scratch: call wg_rx_reserve(%u) first", n, n);
-  } else {
-    if ((rc = rxp_scratch(t, n)) != WG_OK) return rc;
-    if ((rc = rxp_after_last(t, s)) != WG_OK) return rc;
-  }
+  if ((rc = rxp_begin(t, s, capturing, n, kRxDeliverWords)) != WG_OK) return rc;
   wgrp::RxDeliverParams P{};
   P.desc = b->desc;
   P.plan_status = b->plan_status;
@@ -541,14 +410,8 @@ int wg_rx_deliver(wg_ctx* c, const wg_rx_deliver_batch* b, void* stream) {
   P.delivered = b->delivered;
   P.n = n;
   P.part = (uint4*)t->d_part.p;
-  const uint32_t nb = rxp_blocks(n);
-  hipLaunchKernelGGL(wgrp::k_rx_merge, dim3(nb), dim3(256), 0, s, P);
-  hipLaunchKernelGGL(wgrp::k_rx_scan, dim3(1), dim3(256), 0, s, P.part, nb, (uint2*)b->delivered);
-  hipLaunchKernelGGL(wgrp::k_rx_items, dim3(nb), dim3(256), 0, s, P);
-  const hipError_t le = hipGetLastError();
-  if (le != hipSuccess) return fail(WG_EDEVICE, "receive deliver kernels: %s", hipGetErrorString(le));
-  if (!capturing && (rc = rxp_mark(t, s)) != WG_OK) return rc;
-  return WG_OK;
+  rank_launch(wgrp::k_rx_merge, wgrp::k_rx_items, P, b->delivered, s);
+  return plan_end(t->order, s, capturing, kRxDeliverWords);
 }
 
 }  // extern "C"

@@ -65,9 +65,10 @@ struct TxState {
   DevBuf d_pre;    // R x K prefixes of the counts, per column (written by k_tx_scan, advanced by k_tx_emit)
   bool cnt_dirty = false;  // a plan's launches failed part-way: the count matrix is zeroed before the next plan
   DevBuf d_base;   // per key slot: the counter before this plan (broadcast: [0] = packets that passed)
-  hipEvent_t ev = nullptr;  // last use of the counters / scratch, and its stream
-  hipStream_t ev_stream = (hipStream_t)-1;
+  StreamOrder order;  // last plan / counter, peer or route write
 };
+
+const PlanWords kTxWords{"transmit plan", "packets", "wg_tx_reserve"};
 
 // runs R and steps per run for a plan of n packets over K keys
 void tx_geometry(uint32_t n, uint32_t K, uint32_t* runs, uint32_t* spr) {
@@ -83,11 +84,6 @@ uint32_t tx_max_rows(uint32_t n, uint32_t K) {
   return std::max(1u, std::min(nsteps, rmax));
 }
 
-bool tx_capturing(hipStream_t s) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  return hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-}
-
 // The transmit state, allocated at the first wg_tx_* call. Caller holds c->mu.
 int tx_get(wg_ctx* c, TxState** out) {
   if (!c->tx) {
@@ -97,19 +93,13 @@ int tx_get(wg_ctx* c, TxState** out) {
     if ((rc = t->d_send.ensure((size_t)c->key_slots * 8)) != WG_OK ||
         (rc = t->d_peers.ensure((size_t)c->key_slots * 4)) != WG_OK ||
         (rc = t->d_base.ensure((size_t)c->key_slots * 8)) != WG_OK ||
-        (rc = t->d_rhdr.ensure(sizeof(TxRouteHdr))) != WG_OK) {
-      for (DevBuf* b : {&t->d_send, &t->d_peers, &t->d_base, &t->d_rhdr}) b->release();
+        (rc = t->d_rhdr.ensure(sizeof(TxRouteHdr))) != WG_OK)
       return rc;
-    }
-    hipError_t e = hipEventCreateWithFlags(&t->ev, hipEventDisableTiming);
+    hipError_t e = t->order.create();
     if (e == hipSuccess) e = hipMemsetAsync(t->d_send.p, 0, (size_t)c->key_slots * 8, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(t->d_rhdr.p, 0, sizeof(TxRouteHdr), c->stream);  // no routes
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-      for (DevBuf* b : {&t->d_send, &t->d_peers, &t->d_base, &t->d_rhdr}) b->release();
-      if (t->ev) (void)hipEventDestroy(t->ev);
-      return fail(WG_EDEVICE, "transmit state: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(WG_EDEVICE, "transmit state: %s", hipGetErrorString(e));
     c->tx = t.release();
   }
   *out = c->tx;
@@ -117,25 +107,8 @@ int tx_get(wg_ctx* c, TxState** out) {
 }
 
 void tx_free(wg_ctx* c) {
-  if (!c->tx) return;
-  TxState* t = c->tx;
-  for (DevBuf* b : {&t->d_send, &t->d_peers, &t->d_rhdr, &t->d_rent, &t->d_code, &t->d_cnt, &t->d_pre, &t->d_base})
-    b->release();
-  if (t->ev) (void)hipEventDestroy(t->ev);
-  delete t;
+  delete c->tx;
   c->tx = nullptr;
-}
-
-// Orders stream s behind the last plan / counter write (which may sit on another stream), and the
-// next one behind what s does now. Caller holds c->mu.
-int tx_after_last(TxState* t, hipStream_t s) {
-  if (t->ev_stream != s && t->ev_stream != (hipStream_t)-1) HIPTRY(hipStreamWaitEvent(s, t->ev, 0));
-  return WG_OK;
-}
-int tx_mark(TxState* t, hipStream_t s) {
-  HIPTRY(hipEventRecord(t->ev, s));
-  t->ev_stream = s;
-  return WG_OK;
 }
 
 // zero the send counters of key slots [first, first + n) (a new SymmetricKeypair starts at 0,
@@ -145,20 +118,21 @@ int tx_reset_slots(wg_ctx* c, uint32_t first, uint32_t n, hipStream_t s) {
   TxState* t = c->tx;
   if (!t || !n) return WG_OK;
   int rc;
-  if ((rc = tx_after_last(t, s)) != WG_OK) return rc;
+  if ((rc = t->order.after_last(s)) != WG_OK) return rc;
   HIPTRY(hipMemsetAsync((uint64_t*)t->d_send.p + first, 0, (size_t)n * 8, s));
-  return tx_mark(t, s);
+  return t->order.mark(s);
 }
 
-// scratch for plans of up to n packets; never on a capturing stream (the caller checks)
-int tx_scratch(wg_ctx* c, TxState* t, uint32_t n) {
-  const size_t code = (size_t)std::max(n, 1u) * 4;
+// scratch for plans of up to n packets: does it fit, and (plan_reserve) its growth
+bool tx_scratch_fits(const wg_ctx* c, const TxState* t, uint32_t n) {
   const size_t cnt = (size_t)tx_max_rows(n, c->key_slots) * c->key_slots * 4;
-  if (code <= t->d_code.cap && cnt <= t->d_cnt.cap && cnt <= t->d_pre.cap) return WG_OK;
-  HIPTRY(hipDeviceSynchronize());  // the scratch is reallocated under earlier plans
+  return (size_t)std::max(n, 1u) * 4 <= t->d_code.cap && cnt <= t->d_cnt.cap && cnt <= t->d_pre.cap;
+}
+int tx_scratch_grow(wg_ctx* c, TxState* t, uint32_t n) {
+  const size_t cnt = (size_t)tx_max_rows(n, c->key_slots) * c->key_slots * 4;
   int rc;
   t->cnt_dirty = true;  // until the (new) count matrix has been zeroed
-  if ((rc = t->d_code.ensure(code)) != WG_OK || (rc = t->d_cnt.ensure(cnt)) != WG_OK ||
+  if ((rc = t->d_code.ensure((size_t)std::max(n, 1u) * 4)) != WG_OK || (rc = t->d_cnt.ensure(cnt)) != WG_OK ||
       (rc = t->d_pre.ensure(cnt)) != WG_OK)
     return rc;
   HIPTRY(hipMemsetAsync(t->d_cnt.p, 0, t->d_cnt.cap, c->stream));
@@ -451,9 +425,9 @@ int wg_tx_peers_set(wg_ctx* c, const uint32_t* slots, uint32_t n) {
   TxState* t;
   int rc;
   if ((rc = tx_get(c, &t)) != WG_OK) return rc;
-  if ((rc = tx_after_last(t, c->stream)) != WG_OK) return rc;  // no queued plan may see half of the new list
+  if ((rc = t->order.after_last(c->stream)) != WG_OK) return rc;  // no queued plan may see half of the new list
   if (n) HIPTRY(hipMemcpyAsync(t->d_peers.p, slots, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  if ((rc = tx_mark(t, c->stream)) != WG_OK) return rc;
+  if ((rc = t->order.mark(c->stream)) != WG_OK) return rc;
   HIPTRY(hipStreamSynchronize(c->stream));
   t->n_peers = n;
   return WG_OK;
@@ -490,7 +464,7 @@ int wg_routes_set(wg_ctx* c, const wg_prefix* prefixes, const uint32_t* slots, u
   H.entries = (const uint2*)t->d_rent.p;
   HIPTRY(hipMemcpyAsync(t->d_rent.p, ent.data(), ent.size() * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
   HIPTRY(hipMemcpyAsync(t->d_rhdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream));
-  if ((rc = tx_mark(t, c->stream)) != WG_OK) return rc;
+  if ((rc = t->order.mark(c->stream)) != WG_OK) return rc;
   HIPTRY(hipStreamSynchronize(c->stream));
   return WG_OK;
 }
@@ -504,9 +478,9 @@ int wg_tx_counters_set(wg_ctx* c, uint32_t first, uint32_t n, const uint64_t* co
   int rc;
   if ((rc = tx_get(c, &t)) != WG_OK) return rc;
   if (!n) return WG_OK;
-  if ((rc = tx_after_last(t, c->stream)) != WG_OK) return rc;
+  if ((rc = t->order.after_last(c->stream)) != WG_OK) return rc;
   HIPTRY(hipMemcpyAsync((uint64_t*)t->d_send.p + first, counters, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-  if ((rc = tx_mark(t, c->stream)) != WG_OK) return rc;
+  if ((rc = t->order.mark(c->stream)) != WG_OK) return rc;
   HIPTRY(hipStreamSynchronize(c->stream));
   return WG_OK;
 }
@@ -520,7 +494,7 @@ int wg_tx_counters_get(wg_ctx* c, uint32_t first, uint32_t n, uint64_t* counters
   int rc;
   if ((rc = tx_get(c, &t)) != WG_OK) return rc;
   if (!n) return WG_OK;
-  if ((rc = tx_after_last(t, c->stream)) != WG_OK) return rc;  // the counters after every queued plan
+  if ((rc = t->order.after_last(c->stream)) != WG_OK) return rc;  // the counters after every queued plan
   HIPTRY(hipMemcpyAsync(counters, (uint64_t*)t->d_send.p + first, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
   HIPTRY(hipStreamSynchronize(c->stream));
   return WG_OK;
@@ -533,7 +507,7 @@ int wg_tx_reserve(wg_ctx* c, uint32_t max_packets) {
   TxState* t;
   int rc;
   if ((rc = tx_get(c, &t)) != WG_OK) return rc;
-  return tx_scratch(c, t, max_packets);
+  return plan_reserve(tx_scratch_fits(c, t, max_packets), [&] { return tx_scratch_grow(c, t, max_packets); });
 }
 
 int wg_tx_plan(wg_ctx* c, const wg_tx_batch* b, void* stream) {
@@ -543,7 +517,7 @@ int wg_tx_plan(wg_ctx* c, const wg_tx_batch* b, void* stream) {
   hipStream_t s = pick_stream(c, stream);
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  const bool capturing = tx_capturing(s);
+  const bool capturing = stream_capturing(s);
   if (capturing && !c->tx)
     return fail(WG_EINVAL, "transmit plan on a capturing stream before any wg_tx_* call: call wg_tx_reserve first");
   TxState* t;
@@ -556,14 +530,9 @@ int wg_tx_plan(wg_ctx* c, const wg_tx_batch* b, void* stream) {
   if (!b->in || !b->pkt_off || !b->pkt_len) return fail(WG_EINVAL, "NULL tun ring or packet table");
   if (!b->desc_out || (((uintptr_t)b->desc_out) & 15u) || !b->tx_status || (((uintptr_t)b->tx_status) & 3u))
     return fail(WG_EINVAL, "descriptor / status output must be non-NULL and aligned (16 / 4 bytes)");
-  if (capturing) {
-    if ((size_t)n * 4 > t->d_code.cap || (size_t)tx_max_rows(n, c->key_slots) * c->key_slots * 4 > t->d_cnt.cap ||
-        t->cnt_dirty)
-      return fail(WG_EINVAL, "transmit plan of %u packets on a capturing stream needs more scratch: call wg_tx_reserve(%u) first", n, n);
-  } else {
-    if ((rc = tx_scratch(c, t, n)) != WG_OK) return rc;
-    if ((rc = tx_after_last(t, s)) != WG_OK) return rc;
-  }
+  // (under capture a dirty count matrix counts as scratch that does not fit)
+  const bool fits = tx_scratch_fits(c, t, n) && !(capturing && t->cnt_dirty);
+  if ((rc = plan_begin(t->order, s, capturing, fits, [&] { return tx_scratch_grow(c, t, n); }, kTxWords, n)) != WG_OK) return rc;
   wgtx::TxParams P{};
   P.in = b->in;
   P.in_size = b->in_size;
@@ -597,13 +566,7 @@ int wg_tx_plan(wg_ctx* c, const wg_tx_batch* b, void* stream) {
   hipLaunchKernelGGL(wgtx::k_tx_classify, dim3(wgrid), dim3(256), 0, s, P);
   hipLaunchKernelGGL(wgtx::k_tx_scan, dim3((P.K + 3u) / 4u), dim3(256), 0, s, P);
   hipLaunchKernelGGL(wgtx::k_tx_emit, dim3(wgrid), dim3(256), 0, s, P);
-  const hipError_t le = hipGetLastError();
-  if (le != hipSuccess) {
-    t->cnt_dirty = true;
-    return fail(WG_EDEVICE, "transmit plan kernels: %s", hipGetErrorString(le));
-  }
-  if (!capturing && (rc = tx_mark(t, s)) != WG_OK) return rc;
-  return WG_OK;
+  return plan_end(t->order, s, capturing, kTxWords, &t->cnt_dirty);
 }
 
 }  // extern "C"

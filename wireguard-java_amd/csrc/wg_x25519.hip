@@ -341,11 +341,7 @@ __global__ void __launch_bounds__(64) k_x25519(X25519Params P) {
 
 // record k < min(*n_records, n): an initiation's ephemeral under the static private key
 __global__ void __launch_bounds__(64) k_hs_dh(DhParams P) {
-  uint32_t nl = P.n;
-  if (P.n_records) {
-    const uint32_t nr = *P.n_records;
-    nl = nr < nl ? nr : nl;
-  }
+  const uint32_t nl = wgrp::dev_count(P.n_records, P.n);
   if (blockIdx.x * 64u >= nl) return;  // (wave-uniform)
   const uint32_t i = blockIdx.x * 64u + threadIdx.x;
   uint32_t k[8], u[8], out[8];
