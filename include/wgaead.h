@@ -655,8 +655,8 @@ int wg_hs_check(wg_ctx* ctx, const wg_hs_batch* batch, void* stream);
  * wg_x25519_batch is that primitive over descriptors, the analogue of wg_blake2s_batch; wg_hs_dh runs it
  * over wg_hs_check's records with the static private key of wg_hs_static_set, at the end of the plan ->
  * check chain. The KDF and hash chain up to the initiator's static key and the open of encrypted_static
- * follow in the next section (wg_hs_open); the response, the state machine, cookies and timers stay on the
- * host.
+ * follow in the next section (wg_hs_open), the response in the one after it (wg_hs_respond); the state
+ * machine, cookies and timers stay on the host.
  *
  * wg_x25519_batch(ctx, desc, n, in, in_size, out, out_size, status, stream): out[out_off .. out_off + 32)
  *   = X25519(in[scalar_off .. + 32), in[point_off .. + 32)) as X25519.scalarMult computes it
@@ -796,6 +796,77 @@ typedef struct wg_hs_open_batch {
 } wg_hs_open_batch;
 int wg_hs_peers_set(wg_ctx* ctx, const uint8_t* publics_host /* 32 n bytes */, uint32_t n);
 int wg_hs_open(wg_ctx* ctx, const wg_hs_open_batch* batch, void* stream);
+
+/* ---- the answer to an initiation, on the device ----
+ * After wg_hs_open the dearest part of the handshake is left: ResponderHandshake.deriveKeypair
+ * (Handshakes.java:250-287) and OutgoingResponse (OutgoingResponse.java:16-25, ResponsePacket.java:107-117):
+ * a fresh ephemeral key, three X25519 ladders, five HKDFs, an AEAD seal of nothing and a keyed BLAKE2s per
+ * initiation. The device lacks only the randomness, which the host hands in as a buffer. wg_hs_respond turns
+ * wg_hs_open's entries into ready-to-send 92-byte responses and the transport key pairs, bit-exact. With H,
+ * KDFn as in the section above, h / ck / E_i / S_i = the entry's hash / chain_key / remote_ephemeral /
+ * remote_static, e = the clamped ephemeral and psk = 32 zero bytes (the reference's responder, :262):
+ *     Epub = X25519(e, 9)          h = H(h || Epub)         ck = KDF1(ck, Epub)
+ *     ck = KDF1(ck, X25519(e, E_i))                         ck = KDF1(ck, X25519(e, S_i))
+ *     tau = KDF2(ck, psk)   k = KDF3(ck, psk)   ck = KDF1(ck, psk)      (all three from the same ck)
+ *     h = H(h || tau)       empty = ChaCha20-Poly1305-seal(k, nonce 0^12, aad = h, "")   (the 16-byte tag)
+ *     recv_key = KDF1(ck, "")      send_key = KDF2(ck, "")               (:286: the responder sends with T2)
+ *     response = {2, 0,0,0, LE32(local_index), LE32(sender_index), Epub, empty,
+ *                 mac1 = BLAKE2s-128(key = H("mac1----" || S_i), response[0 .. 60)), mac2 = 0^16}
+ *   A low-order E_i or S_i gives an all-zero secret and goes through (the reference ignores the agreement's
+ *   false). The final h is needed by nobody and is not stored.
+ *
+ * wg_hs_respond(ctx, b, stream): for every k < min(*n_inits, n) (n_inits: a device pointer, usually
+ *   &wg_hs_open_summary.n_emitted; NULL: all n), in this order:
+ *   1. flags has WG_HS_RESP_SKIP_NEWPEER and inits[k].peer == WG_HS_NOPEER: WG_HS_RESP_NOPEER (wg_hs_open left
+ *   that entry's chain_key before the static-static step: the chain must not go on from it). Without the flag
+ *   the caller vouches that every entry's chain_key is final, and peer is only copied through.
+ *   2. the 32 bytes ephemerals[32 k ..) are all zero, tested before clamping: WG_HS_RESP_NOEPH. 3. WG_HS_RESP_OK.
+ *   ephemerals holds fresh private keys from the host's CSPRNG, clamped on the device as every scalar is; it
+ *   is input AND output: the call zeroes each one it consumed and leaves a non-OK entry's untouched, so a
+ *   replay of a captured graph without a refresh answers nothing (all NOEPH). local_index[k] is the
+ *   responder's new session index, as allocateNewSessionIndex would choose it on the host. resp_status[k] is
+ *   written for the covered k and nothing behind them. sessions[0 .. n_ok) is the stable compaction of the
+ *   OK entries: {index = inits[k].index, init = k, peer = inits[k].peer, local_index = local_index[k],
+ *   response, remote_index = inits[k].sender_index, send_key, recv_key}; every byte of a written session is
+ *   defined and nothing behind n_ok sessions is touched. summary = {n_ok, n_nopeer, n_noeph, 0}. n = 0 is a
+ *   no-op. Without a private key: WG_ENOKEY. Unknown flag bits: WG_EINVAL. n above 2^30: WG_E2BIG. inits, ephemerals, sessions:
+ *   16-byte aligned; summary: 8; the others: 4. An output (ephemerals among them) that overlaps another output
+ *   or an input: WG_EINVAL. Scratch (272 bytes per entry, holding DH results and keys only for the time of
+ *   the call) is sized by wg_hs_reserve; a call that needs more allocates it, except on a capturing stream
+ *   (WG_EINVAL: reserve first); wg_ctx_destroy wipes it. Four launches (ladders, chain, scan, emit), no wait
+ *   between workgroups, nothing about a call on the host: a captured plan + check + dh + open + respond
+ *   replays; between replays the host refreshes ephemerals and local_index in place. The three ladders of an
+ *   entry run in three neighbouring lanes. No branch, address or loop bound depends on an ephemeral's value, a
+ *   DH result, ck, tau, k or a transport key, except the all-zero test of the raw ephemeral. The host installs
+ *   send_key / recv_key with wg_keys_set and local_index with wg_rx_sessions_set. */
+#define WG_HS_RESP_OK 0u
+#define WG_HS_RESP_NOPEER 1u       /* SKIP_NEWPEER, and the entry's peer is WG_HS_NOPEER */
+#define WG_HS_RESP_NOEPH 2u        /* the entry's ephemeral is all zero */
+#define WG_HS_RESP_SKIP_NEWPEER 1u /* flags: do not answer an entry whose peer is WG_HS_NOPEER */
+typedef struct wg_hs_session { /* 176 bytes */
+  uint32_t index;       /* batch index of the initiation's datagram */
+  uint32_t init;        /* position in inits */
+  uint32_t peer;        /* inits[init].peer */
+  uint32_t local_index; /* the responder's session index used */
+  uint8_t response[92]; /* the wire message */
+  uint32_t remote_index; /* inits[init].sender_index */
+  uint8_t send_key[32];
+  uint8_t recv_key[32];
+} wg_hs_session;
+typedef struct wg_hs_respond_summary {
+  uint32_t n_ok, n_nopeer, n_noeph, _zero;
+} wg_hs_respond_summary;
+typedef struct wg_hs_respond_batch {
+  const wg_hs_init* inits;        /* device, 16-byte aligned: wg_hs_open's entries, or the caller's */
+  const uint32_t* n_inits;        /* device: &wg_hs_open_summary.n_emitted; NULL: all n */
+  uint8_t* ephemerals;            /* device, 16-byte aligned, n * 32 bytes; in and out */
+  const uint32_t* local_index;    /* device, n entries */
+  uint32_t* resp_status;          /* device, n entries, WG_HS_RESP_* */
+  wg_hs_session* sessions;        /* device, 16-byte aligned, n entries */
+  wg_hs_respond_summary* summary; /* device, 16 bytes, 8-byte aligned */
+  uint32_t n, flags;
+} wg_hs_respond_batch;
+int wg_hs_respond(wg_ctx* ctx, const wg_hs_respond_batch* batch, void* stream);
 
 int wg_seal1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* pt, uint32_t len, uint8_t* out);
 int wg_open1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* in, uint32_t len, uint8_t* pt);

@@ -62,6 +62,10 @@ WG_HS_OPEN_BADAUTH = 2
 WG_HS_OPEN_SKIPPED = 3
 WG_HS_OPEN_BADDESC = 4
 WG_HS_NOPEER = 0xFFFFFFFF
+WG_HS_RESP_OK = 0
+WG_HS_RESP_NOPEER = 1
+WG_HS_RESP_NOEPH = 2
+WG_HS_RESP_SKIP_NEWPEER = 1
 WG_MAX_FILTERS = 65536
 WG_NO_FILTER = 0xFFFFFFFF
 WG_LEN_INVALID = 0xFFFFFFFF
@@ -211,6 +215,26 @@ class WgHsOpenBatch(ctypes.Structure):
                 ("summary", ctypes.c_void_p), ("n", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
 
 
+class WgHsSession(ctypes.Structure):
+    """wg_hs_session: one answered initiation of wg_hs_respond."""
+    _fields_ = [("index", ctypes.c_uint32), ("init", ctypes.c_uint32), ("peer", ctypes.c_uint32),
+                ("local_index", ctypes.c_uint32), ("response", ctypes.c_uint8 * 92), ("remote_index", ctypes.c_uint32),
+                ("send_key", ctypes.c_uint8 * 32), ("recv_key", ctypes.c_uint8 * 32)]
+
+
+class WgHsRespondSummary(ctypes.Structure):
+    """wg_hs_respond_summary: totals of one wg_hs_respond call."""
+    _fields_ = [("n_ok", ctypes.c_uint32), ("n_nopeer", ctypes.c_uint32), ("n_noeph", ctypes.c_uint32),
+                ("_zero", ctypes.c_uint32)]
+
+
+class WgHsRespondBatch(ctypes.Structure):
+    """wg_hs_respond_batch: one wg_hs_respond call (device pointers)."""
+    _fields_ = [("inits", ctypes.c_void_p), ("n_inits", ctypes.c_void_p), ("ephemerals", ctypes.c_void_p),
+                ("local_index", ctypes.c_void_p), ("resp_status", ctypes.c_void_p), ("sessions", ctypes.c_void_p),
+                ("summary", ctypes.c_void_p), ("n", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
 class WgCompletion(ctypes.Structure):
     """wg_completion: one reaped packet of a wg_queue."""
     _fields_ = [("user", ctypes.c_uint64), ("counter", ctypes.c_uint64), ("data", ctypes.c_void_p),
@@ -232,6 +256,7 @@ assert ctypes.sizeof(WgB2sDesc) == 32 and ctypes.sizeof(WgHsRecord) == 160 and c
 assert ctypes.sizeof(WgHsBatch) == 80
 assert ctypes.sizeof(WgX25519Desc) == 32 and ctypes.sizeof(WgHsDhBatch) == 40
 assert ctypes.sizeof(WgHsInit) == 144 and ctypes.sizeof(WgHsOpenSummary) == 16 and ctypes.sizeof(WgHsOpenBatch) == 64
+assert ctypes.sizeof(WgHsSession) == 176 and ctypes.sizeof(WgHsRespondSummary) == 16 and ctypes.sizeof(WgHsRespondBatch) == 64
 assert ctypes.sizeof(WgPkt) == 32 and ctypes.sizeof(WgAeadDesc) == 64 and ctypes.sizeof(WgPrefix) == 18
 
 # (name, restype, argtypes) for every symbol include/wgaead.h declares
@@ -282,6 +307,7 @@ SIGNATURES = [
     ("wg_hs_dh", _I, [_VP, ctypes.POINTER(WgHsDhBatch), _VP]),
     ("wg_hs_peers_set", _I, [_VP, _VP, _U32]),
     ("wg_hs_open", _I, [_VP, ctypes.POINTER(WgHsOpenBatch), _VP]),
+    ("wg_hs_respond", _I, [_VP, ctypes.POINTER(WgHsRespondBatch), _VP]),
     ("wg_seal1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_open1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_pp_config", _I, [_VP, _U32, _U32]),

@@ -53,14 +53,17 @@ struct HsState {
   // table, the publics behind 32 B that hold the private key while the secrets are computed, the secrets, the
   // k_x25519 descriptors and statuses that compute them; per record the open's results, per range its counts
   DevBuf d_phdr, d_pempty, d_pslots, d_pin, d_psec, d_pdesc, d_ores, d_opart;
+  // wg_hs_respond.hip: per entry the three ladders' results (96 B) and the session (176 B), per range its counts
+  DevBuf d_rlad, d_rres, d_rpart;
   uint32_t n_peers = 0;
   bool has_key = false;
   bool has_priv = false;
-  StreamOrder order;  // last check / open: they share the scratch
+  StreamOrder order;  // last check / open / respond: they share the scratch
 };
 
 const PlanWords kHsCheckWords{"handshake check", "datagrams", "wg_hs_reserve"};
 const PlanWords kHsOpenWords{"handshake open", "records", "wg_hs_reserve"};
+const PlanWords kHsRespWords{"handshake respond", "entries", "wg_hs_reserve"};
 
 // The handshake state, allocated at the first wg_hs_* call. Caller holds c->mu.
 int hs_get(wg_ctx* c, HsState** out) {
@@ -94,8 +97,8 @@ void hs_free(wg_ctx* c) {
     (void)hipDeviceSynchronize();
     (void)hipMemsetAsync(t->d_key.p, 0, 64, c->stream);
     if (t->d_priv.p) (void)hipMemsetAsync(t->d_priv.p, 0, 32, c->stream);
-    // the peers' static-static secrets, and what the last open derived from them
-    for (DevBuf* b : {&t->d_psec, &t->d_pin, &t->d_ores})
+    // the peers' static-static secrets, what the last open derived from them, and the last respond's scratch
+    for (DevBuf* b : {&t->d_psec, &t->d_pin, &t->d_ores, &t->d_rlad, &t->d_rres})
       if (b->p) (void)hipMemsetAsync(b->p, 0, b->cap, c->stream);
     (void)hipStreamSynchronize(c->stream);
   }
@@ -116,6 +119,20 @@ int hs_scratch_grow(HsState* t, uint32_t n, bool open) {
   if (t->d_ores.p && t->d_ores.cap < (size_t)std::max(n, 1u) * 112) HIPTRY(hipMemset(t->d_ores.p, 0, t->d_ores.cap));  // freed: wiped first
   if ((rc = t->d_opart.ensure(part)) != WG_OK) return rc;
   return t->d_ores.ensure((size_t)std::max(n, 1u) * 112);
+}
+
+// the scratch of wg_hs_respond for n entries (96 + 176 B per entry, per range its counts), and its growth
+bool hs_resp_fits(const HsState* t, uint32_t n) {
+  const size_t m = std::max(n, 1u);
+  return (size_t)std::max(rank_blocks(n), 1u) * 16 <= t->d_rpart.cap && m * 96 <= t->d_rlad.cap && m * 176 <= t->d_rres.cap;
+}
+int hs_resp_grow(HsState* t, uint32_t n) {
+  const size_t m = std::max(n, 1u);
+  int rc;
+  for (DevBuf* b : {&t->d_rlad, &t->d_rres})  // freed when they grow: wiped first
+    if (b->p) HIPTRY(hipMemset(b->p, 0, b->cap));
+  if ((rc = t->d_rpart.ensure((size_t)std::max(rank_blocks(n), 1u) * 16)) != WG_OK || (rc = t->d_rlad.ensure(m * 96)) != WG_OK) return rc;
+  return t->d_rres.ensure(m * 176);
 }
 
 int hs_begin(HsState* t, hipStream_t s, bool capturing, uint32_t n, bool open, const PlanWords& w) {
@@ -457,7 +474,10 @@ int wg_hs_reserve(wg_ctx* c, uint32_t max_messages) {
   HsState* t;
   int rc;
   if ((rc = hs_get(c, &t)) != WG_OK) return rc;
-  return plan_reserve(hs_scratch_fits(t, max_messages, true), [&] { return hs_scratch_grow(t, max_messages, true); });
+  return plan_reserve(hs_scratch_fits(t, max_messages, true) && hs_resp_fits(t, max_messages), [&] {
+    const int grc = hs_scratch_grow(t, max_messages, true);
+    return grc != WG_OK ? grc : hs_resp_grow(t, max_messages);
+  });
 }
 
 int wg_hs_check(wg_ctx* c, const wg_hs_batch* b, void* stream) {

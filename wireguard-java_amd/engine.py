@@ -42,6 +42,9 @@ WG_HS_RECORD_DTYPE = np.dtype([("index", "<u4"), ("len", "<u4"), ("msg", "u1", (
 WG_HS_INIT_DTYPE = np.dtype([("index", "<u4"), ("record", "<u4"), ("sender_index", "<u4"), ("peer", "<u4"),
                              ("remote_ephemeral", "u1", (32,)), ("remote_static", "u1", (32,)), ("hash", "u1", (32,)),
                              ("chain_key", "u1", (32,))])
+WG_HS_SESSION_DTYPE = np.dtype([("index", "<u4"), ("init", "<u4"), ("peer", "<u4"), ("local_index", "<u4"),
+                                ("response", "u1", (92,)), ("remote_index", "<u4"), ("send_key", "u1", (32,)),
+                                ("recv_key", "u1", (32,))])
 
 
 def pack_b2s_desc(in_off, out_off, key_off, length, outlen, keylen) -> np.ndarray:
@@ -402,8 +405,8 @@ class Engine:
         L.check(self._lib.wg_hs_key_set(self.ctx, pub.ctypes.data))
 
     def hs_reserve(self, max_messages: int) -> None:
-        """wg_hs_reserve: scratch for checks of up to max_messages datagrams (needed before a check is
-        captured into a graph: a capturing stream cannot allocate)."""
+        """wg_hs_reserve: scratch for checks, opens and responds of up to max_messages datagrams (needed before
+        one is captured into a graph: a capturing stream cannot allocate)."""
         L.check(self._lib.wg_hs_reserve(self.ctx, max_messages))
 
     def hs_check(self, wire, pkt_off, pkt_len, hs_status, records, hs_summary, host_list=None, rx_summary=None,
@@ -544,6 +547,52 @@ class Engine:
         if not int(d_sum.cpu().numpy()[0]):
             return status, None
         return status, d_init.cpu().numpy().reshape(-1).view(WG_HS_INIT_DTYPE)[0]
+
+    # ---- the answer to an initiation (wg_hs_respond) ------------------------------------------
+    def hs_respond(self, inits, open_summary, ephemerals, local_index, resp_status, sessions, resp_summary,
+                   skip_newpeer: bool = True, stream: int | None = None) -> None:
+        """wg_hs_respond over torch tensors: inits uint8 [n, 144] and open_summary int32 [4] as hs_open() wrote
+        them (the entry count, n_emitted, is read on the device: open and respond run back to back on one stream;
+        open_summary None: all n entries), ephemerals uint8 [n, 32] or [n * 32] (fresh private keys from the
+        host's CSPRNG; the call zeroes each one it consumed), local_index int32 [n] (the responder's new session
+        indices), resp_status int32 [n] (WG_HS_RESP_*), sessions uint8 [n, 176] (wg_hs_session,
+        WG_HS_SESSION_DTYPE), resp_summary int32 [4] (n_ok, n_nopeer, n_noeph, 0). skip_newpeer: an entry without
+        a peer is not answered (its chain_key is not final); without it the caller vouches for every chain_key."""
+        n_inits = open_summary.data_ptr() + L.WgHsOpenSummary.n_emitted.offset if open_summary is not None else None
+        b = L.WgHsRespondBatch(inits.data_ptr(), n_inits, ephemerals.data_ptr(), local_index.data_ptr(),
+                               resp_status.data_ptr(), sessions.data_ptr(), resp_summary.data_ptr(), inits.shape[0],
+                               L.WG_HS_RESP_SKIP_NEWPEER if skip_newpeer else 0)
+        L.check(self._lib.wg_hs_respond(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def hs_respond_host(self, init_entry, ephemeral, local_index: int):
+        """One wg_hs_init entry (a WG_HS_INIT_DTYPE scalar whose chain_key is final) through hs_respond with this
+        ephemeral private key (32 bytes) and session index: returns (WG_HS_RESP_* status, the wg_hs_session as a
+        WG_HS_SESSION_DTYPE scalar, or None when nothing was answered). The device copies of the ephemeral and
+        of the session are zeroed before it returns. For the noise mirror and tests."""
+        import torch
+        if len(ephemeral) != 32:
+            raise L.WgError(L.WG_EINVAL, "an ephemeral private key is 32 bytes")
+        dev = torch.device("cuda", self.device)
+        ent = np.zeros(1, WG_HS_INIT_DTYPE)
+        ent[0] = init_entry
+        d_init = torch.from_numpy(ent.view(np.uint8).reshape(1, 144)).to(dev)
+        d_eph = torch.from_numpy(np.frombuffer(bytes(ephemeral), np.uint8).copy()).to(dev)
+        d_li = torch.from_numpy(np.array([local_index & 0xFFFFFFFF], np.uint32).view(np.int32)).to(dev)
+        d_st = torch.zeros(1, dtype=torch.int32, device=dev)
+        d_sess = torch.zeros((1, 176), dtype=torch.uint8, device=dev)
+        d_sum = torch.zeros(4, dtype=torch.int32, device=dev)
+        st = _torch_stream()
+        try:
+            self.hs_respond(d_init, None, d_eph, d_li, d_st, d_sess, d_sum, skip_newpeer=False, stream=st)
+            self.sync(st)
+            status = int(d_st.cpu().numpy()[0])
+            sess = d_sess.cpu().numpy().reshape(-1).view(WG_HS_SESSION_DTYPE)[0].copy() if int(d_sum.cpu().numpy()[0]) else None
+        finally:
+            d_eph.zero_()
+            d_sess.zero_()
+            d_init.zero_()
+            torch.cuda.synchronize(dev)
+        return status, sess
 
     def set_receivers(self, receivers) -> None:
         """wg_ctx_set_receivers: device tensor of receiver_index per key slot for

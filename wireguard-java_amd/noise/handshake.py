@@ -1,5 +1,5 @@
 """ax.xz.wireguard.noise.handshake mirror: SymmetricKeypair, the drop-in boundary, and
-Handshakes.decryptRemoteStatic, the responder's first phase on the device.
+Handshakes.decryptRemoteStatic / ResponderHandshake, the responder's two phases on the device.
 
 Keeps the reference API (SymmetricKeypair.java:20-94): cipher(src, dst) -> counter,
 decipher(counter, src, dst) raising BadPaddingException (AEADBadTagException),
@@ -9,13 +9,14 @@ API (cipher_batch / decipher_batch) feeds whole device-resident batches.
 """
 from __future__ import annotations
 
+import os
 import threading
 
 import numpy as np
 
 from .. import _lib as L
 from ..engine import Engine, default_engine, desc_as_int64, pack_desc
-from .crypto import AEADBadTagException, IllegalStateException, _bytes, _size, _write
+from .crypto import AEADBadTagException, Crypto, IllegalStateException, _bytes, _size, _write
 from .keys import NoisePrivateKey, NoisePublicKey
 
 
@@ -38,6 +39,58 @@ class Handshakes:
         if init is None:
             raise L.WgError(L.WG_EINVAL, f"wg_hs_open status {status}")
         return NoisePublicKey(init["remote_static"].tobytes())
+
+    @staticmethod
+    def responderHandshake(localKeypair: NoisePrivateKey, remoteEphemeral: NoisePublicKey, encryptedStatic,
+                           encryptedTimestamp, engine: Engine | None = None, ephemeral=None,
+                           localIndex: int = 0) -> "ResponderHandshake":
+        """Handshakes.responderHandshake (Handshakes.java:47-50): both phases of the responder, on the device."""
+        return ResponderHandshake(localKeypair, remoteEphemeral, encryptedStatic, encryptedTimestamp, engine, ephemeral,
+                                  localIndex)
+
+
+class ResponderHandshake:
+    """Handshakes.ResponderHandshake (Handshakes.java:166-303): decryptRemoteStatic through wg_hs_dh + wg_hs_open,
+    deriveKeypair and the response message through wg_hs_respond. `ephemeral` is the fresh ephemeral private key
+    (None: 32 bytes of os.urandom, as NoisePrivateKey.newPrivateKey draws them); localIndex is the responder's
+    session index in the response. Like the reference it answers an initiator no peer table holds: for such an
+    entry wg_hs_open stops before the static-static step, which one ladder and one KDF1 finish here."""
+
+    def __init__(self, localKeypair: NoisePrivateKey, remoteEphemeral: NoisePublicKey, encryptedStatic, encryptedTimestamp,
+                 engine: Engine | None = None, ephemeral=None, localIndex: int = 0):
+        eng = engine or default_engine()
+        eng.hs_static_set(localKeypair.data())
+        status, init = eng.hs_open_host(remoteEphemeral.data(), _bytes(encryptedStatic), _bytes(encryptedTimestamp))
+        if status == L.WG_HS_OPEN_BADAUTH:
+            raise AEADBadTagException("Tag mismatch")
+        if init is None:
+            raise L.WgError(L.WG_EINVAL, f"wg_hs_open status {status}")
+        init = init.copy()
+        if status == L.WG_HS_OPEN_NEWPEER:  # Handshakes.java:232-233
+            (ss, _), = eng.x25519_host([(localKeypair.data(), init["remote_static"].tobytes())])
+            init["chain_key"] = np.frombuffer(Crypto.deriveKey(init["chain_key"].tobytes(), ss), np.uint8)
+        eph = bytes(ephemeral.data() if isinstance(ephemeral, NoisePrivateKey) else ephemeral) if ephemeral is not None \
+            else os.urandom(32)
+        rs, sess = eng.hs_respond_host(init, eph, localIndex)
+        if sess is None:
+            raise L.WgError(L.WG_EINVAL, f"wg_hs_respond status {rs}")
+        self.response = sess["response"].tobytes()
+        self._remote = NoisePublicKey(init["remote_static"].tobytes())
+        self._keypair = SymmetricKeypair(sess["send_key"].tobytes(), sess["recv_key"].tobytes(), engine=eng)
+        sess["send_key"] = 0
+        sess["recv_key"] = 0
+
+    def getKeypair(self) -> "SymmetricKeypair":
+        return self._keypair
+
+    def getRemotePublicKey(self) -> NoisePublicKey:
+        return self._remote
+
+    def getEncryptedEmpty(self) -> bytes:
+        return self.response[44:60]
+
+    def getLocalEphemeral(self) -> NoisePublicKey:
+        return NoisePublicKey(self.response[12:44])
 
 
 class SymmetricKeypair:
