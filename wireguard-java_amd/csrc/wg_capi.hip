@@ -815,6 +815,7 @@ int launch_after_seal(wg_ctx* c, const wg_batch* sb, const wg_batch* ob, hipStre
 #include "wg_rxplan.hip"
 #include "wg_hs.hip"
 #include "wg_x25519.hip"
+#include "wg_hs_chain.hip"
 #include "wg_hs_open.hip"
 #include "wg_hs_respond.hip"
 

@@ -141,6 +141,28 @@ int hs_begin(HsState* t, hipStream_t s, bool capturing, uint32_t n, bool open, c
 
 int hs_open_rekey(wg_ctx* c, HsState* t, const uint8_t* static_public);  // wg_hs_open.hip
 
+// The buffers of a call (wg_hs_open, wg_hs_respond): an empty range overlaps nothing.
+struct HsRange {
+  const void* p;
+  uint64_t bytes;
+};
+bool hs_overlap(const HsRange& a, const HsRange& b) {
+  const uintptr_t x = (uintptr_t)a.p, y = (uintptr_t)b.p;
+  return a.bytes && b.bytes && x < y + b.bytes && y < x + a.bytes;
+}
+// 0: the outputs are disjoint from one another and from the inputs; 1: the first overlap found, walking the
+// outputs in order, is with a later output; 2: it is with an input
+template <int NO, int NI>
+int hs_ranges_overlap(const HsRange (&out)[NO], const HsRange (&in)[NI]) {
+  for (int i = 0; i < NO; ++i) {
+    for (int j = i + 1; j < NO; ++j)
+      if (hs_overlap(out[i], out[j])) return 1;
+    for (int j = 0; j < NI; ++j)
+      if (hs_overlap(out[i], in[j])) return 2;
+  }
+  return 0;
+}
+
 }  // namespace
 
 // ---- device -------------------------------------------------------------------------------

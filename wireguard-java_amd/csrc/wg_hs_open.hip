@@ -1,5 +1,5 @@
 // wg_hs_open.hip — the initiations' encrypted static, opened on the device (included by wg_capi.hip after
-// wg_x25519.hip).
+// wg_hs_chain.hip).
 //
 // wg_hs_check admits a handshake message on its mac1, which needs only the local static PUBLIC key; wg_hs_dh
 // spends a ladder on each admitted initiation. The first test that only a holder of a private key passes comes
@@ -23,19 +23,23 @@
 // is four compressions (the two key blocks K ^ 0x36.., K ^ 0x5c.. as words, never bytes; the message; the
 // inner digest); with CK0 as the key the two key-block states are the constants below, and KDF2 / KDF1 of one
 // salt and ikm share the extract, the key-block states of the expand and T1. The compressions are the steps
-// of ONE loop around ONE b2s_compress: each step's case sets the state and the message block from the
-// lane's registers, a second case puts the result where it belongs. 28 inlined copies would be some 200 KB
-// of straight-line code that every wave streams through the instruction cache once; the loop is 17 KB and
-// stays there. The step number is uniform, so the cases are scalar branches and nothing is indexed
-// dynamically. The AEAD sits in front of step 17: two register chacha20_blocks (counter 0: the Poly1305
-// key; counter 1: the 32 bytes), Poly1305 over aad (32) || ct (32) || LE64(32) || LE64(32) as five Horner
-// steps, the tag compared in all 16 bytes. Then the probe, for the authentic lanes only; a wave without a
-// known peer skips the static-static KDF (steps 19-26).
+// of kOpenProgram (wg_hs_chain.h), written once in the order of the chain above, and run by the machine of
+// wg_hs_chain.hip: ONE loop around ONE b2s_compress, in which the step's word names its source, its
+// operation and its destination. 28 inlined copies would be some 200 KB of straight-line code that every
+// wave streams through the instruction cache once; the loop stays there. The step counter is uniform, so
+// the switches are scalar branches and nothing is indexed dynamically. What this kernel adds to the generic
+// operations: its sources (the record's ephemeral, ss, the peer's static-static secret), H(H(H0 || S_pub)
+// || E), the two blocks of H(h || encrypted_static), H(h || encrypted_timestamp) and "ck if the lane has a
+// peer". The AEAD sits in front of the first block of H(h || encrypted_static) (OP_ES1), its key being the
+// T2 that the step before left in the state: two register chacha20_blocks (counter 0: the Poly1305 key;
+// counter 1: the 32 bytes), wghc::poly_tag over aad (32) || ct (32) || LE64(32) || LE64(32), the tag compared
+// in all 16 bytes. Then the probe, for the authentic lanes only; a wave without a known peer jumps over the
+// static-static KDF, the eight steps [kOpenStaticBegin, kOpenStaticEnd) that the header finds in the program.
 //
 // Constant time: no branch, address or loop bound depends on ss, on a derived key or on the static-static
-// secret. The branches depend on the record's length, the statuses, the tag comparison's outcome and the
-// decrypted static key of an authentic message (the probe); the static-static secret's ADDRESS depends on
-// which peer it is, not on its value.
+// secret. The program is public and indexed by a public counter. The branches depend on the program, the
+// record's length, the statuses, the tag comparison's outcome and the decrypted static key of an authentic
+// message (the probe); the static-static secret's ADDRESS depends on which peer it is, not on its value.
 //
 // Peers. wg_hs_peers_set keeps the peers' static public keys on the device, each peer's X25519(S_priv, peer)
 // beside them (one k_x25519 launch), and an open-addressing table over them in wg_rx_sessions_set's manner:
@@ -78,30 +82,6 @@ struct OpenParams {
 
 __device__ __forceinline__ uint32_t open_len(const OpenParams& P) { return wgrp::dev_count(P.n_records, P.n); }
 
-__device__ __forceinline__ void set8(uint32_t d[8], const uint32_t s[8]) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) d[j] = s[j];
-}
-// m = the 32 bytes w, zeros behind them
-__device__ __forceinline__ void msg32(uint32_t m[16], const uint32_t w[8]) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    m[j] = w[j];
-    m[8 + j] = 0u;
-  }
-}
-// m = the HMAC key block of a 32-byte key: key ^ pad, then pad (pad = 0x36363636 / 0x5c5c5c5c)
-__device__ __forceinline__ void pad_block(uint32_t m[16], const uint32_t key[8], uint32_t pad) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    m[j] = key[j] ^ pad;
-    m[8 + j] = pad;
-  }
-}
-__device__ __forceinline__ void put8(uint32_t w[8], const uint4 a, const uint4 b) {
-  w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-}
-
 // peer + 1 of a static public key, 0 if the table does not hold it
 __device__ __forceinline__ uint32_t hs_peer(const HsPeerHdr& H, const uint32_t w[8]) {
   uint32_t b = hs_peer_bucket(w[0], w[1]);
@@ -123,21 +103,8 @@ __device__ __forceinline__ uint32_t open_static(const uint32_t key[8], const uin
                                                 uint32_t rs[8]) {
   uint32_t ks[16];
   wgd::chacha20_block(key, 0u, 0u, 0u, 0u, ks);
-  uint32_t r[5], s5[5], h[5] = {0u, 0u, 0u, 0u, 0u}, c[5];
-  wgd::poly_r_limbs(ks[0], ks[1], ks[2], ks[3], r);
-  wgd::poly_scale5(r, s5);
-  const uint32_t s0 = ks[4], s1 = ks[5], s2 = ks[6], s3 = ks[7];
-#pragma unroll
-  for (int b = 0; b < 5; ++b) {
-    if (b < 2) wgd::poly_block_limbs(aad[4 * b], aad[4 * b + 1], aad[4 * b + 2], aad[4 * b + 3], 1u << 24, c);
-    else if (b < 4) wgd::poly_block_limbs(es[4 * b - 8], es[4 * b - 7], es[4 * b - 6], es[4 * b - 5], 1u << 24, c);
-    else wgd::poly_block_limbs(32u, 0u, 32u, 0u, 1u << 24, c);
-#pragma unroll
-    for (int j = 0; j < 5; ++j) h[j] += c[j];
-    wgd::poly_mul<false>(h, r, s5);
-  }
   uint32_t tag[4];
-  wgd::poly_finish(h, s0, s1, s2, s3, tag);
+  wghc::poly_tag<2>(ks, aad, es, tag);
   const uint32_t diff = (tag[0] ^ es[8]) | (tag[1] ^ es[9]) | (tag[2] ^ es[10]) | (tag[3] ^ es[11]);  // all 16 bytes
   wgd::chacha20_block(key, 1u, 0u, 0u, 0u, ks);
 #pragma unroll
@@ -171,92 +138,48 @@ __global__ void __launch_bounds__(256) k_hs_open(OpenParams P) {
       else go = true;
     }
     const HsPeerHdr H = *P.peers;
-    uint32_t hh[8], ck[8], ist[8], ost[8], x[8], st[8], m[16];
+    using namespace wghc;
+    Chain c;
+    clear(c);
+    set8(c.ist, kCk0Ipad);  // KDF1(CK0, E) starts from the constant key-block states
+    set8(c.ost, kCk0Opad);
     uint32_t peer = 0;     // peer + 1 of an authentic lane with a known static key
     bool auth = false;
     bool any_known = false;
-    uint32_t t = 0;
-    bool last = true;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) hh[j] = ck[j] = ist[j] = ost[j] = x[j] = st[j] = 0u;
+    Step s = fetch(kOpenProgram, 0u);
 #pragma unroll 1
-    for (uint32_t step = 0; step < 28u; ++step) {
-      if (step == 19u && !any_known) step = 27u;  // (wave-uniform) no static-static KDF to run
-      switch (step) {
-        case 0: {  // h = H(H(H0 || S_pub) || E)
+    for (uint32_t step = 0; step < kOpenSteps;) {
+      uint32_t src[8];
+      switch (s.arg) {
+        case SRC_E: put8(src, rec[1], rec[2]); break;
+        case SRC_SS: put8(src, shr[0], shr[1]); break;
+        case SRC_STATIC: {  // (a lane without a peer: zeros, and the result is dropped)
+          uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
+          if (peer) {
+            const uint4* q = (const uint4*)(H.secrets + 32ull * (peer - 1u));
+            a = q[0];
+            b = q[1];
+          }
+          put8(src, a, b);
+          break;
+        }
+        default: source(c, s.arg, src); break;
+      }
+      switch (s.op) {
+        case OP_H0: {  // h = H(H(H0 || S_pub) || E)
           const uint4* q = (const uint4*)P.hs0;
-          put8(m, q[0], q[1]);
-          put8(m + 8, rec[1], rec[2]);
-          wghs::b2s_init(st, 32u, 0u);
-          t = 64u; last = true;
+          put8(c.m, q[0], q[1]);
+          put8(c.m + 8, rec[1], rec[2]);
+          wghs::b2s_init(c.st, 32u, 0u);
+          c.t = 64u; c.last = true;
           break;
         }
-        case 1: {  // KDF1(CK0, E): the extract's inner hash from the constant state
-          uint32_t e[8];
-          put8(e, rec[1], rec[2]);
-          msg32(m, e);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) st[j] = kCk0Ipad[j];
-          t = 96u; last = true;
-          break;
-        }
-        case 2:  // ... and its outer hash: the PRK
-          msg32(m, st);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) st[j] = kCk0Opad[j];
-          t = 96u; last = true;
-          break;
-        case 3: case 11: case 23:  // the expand's key blocks, PRK ^ ipad / PRK ^ opad
-          pad_block(m, x, 0x36363636u);
-          wghs::b2s_init(st, 32u, 0u);
-          t = 64u; last = false;
-          break;
-        case 4: case 12: case 24:
-          pad_block(m, x, 0x5C5C5C5Cu);
-          wghs::b2s_init(st, 32u, 0u);
-          t = 64u; last = false;
-          break;
-        case 5: case 13: case 25:  // T1 = HMAC(PRK, 0x01): inner
-#pragma unroll
-          for (int j = 0; j < 16; ++j) m[j] = j == 0 ? 1u : 0u;
-          set8(st, ist);
-          t = 65u; last = true;
-          break;
-        case 6: case 10: case 14: case 16: case 22: case 26:  // an HMAC's outer hash over the inner digest
-          msg32(m, st);
-          set8(st, ost);
-          t = 96u; last = true;
-          break;
-        case 7: case 19:  // the next extract's key blocks, ck ^ ipad / ck ^ opad
-          pad_block(m, ck, 0x36363636u);
-          wghs::b2s_init(st, 32u, 0u);
-          t = 64u; last = false;
-          break;
-        case 8: case 20:
-          pad_block(m, ck, 0x5C5C5C5Cu);
-          wghs::b2s_init(st, 32u, 0u);
-          t = 64u; last = false;
-          break;
-        case 9: {  // KDF(ck, ss): the extract's inner hash
-          uint32_t w[8];
-          put8(w, shr[0], shr[1]);
-          msg32(m, w);
-          set8(st, ist);
-          t = 96u; last = true;
-          break;
-        }
-        case 15:  // T2 = HMAC(PRK, T1 || 0x02): inner (T1 is the new ck)
-          msg32(m, ck);
-          m[8] = 2u;
-          set8(st, ist);
-          t = 97u; last = true;
-          break;
-        case 17: {  // st = T2 = the key: open encrypted_static; then h = H(h || encrypted_static), first block
+        case OP_ES1: {  // st = T2 = the key: open encrypted_static; then h = H(h || encrypted_static), first block
           uint32_t es[12], rs[8];
           put8(es, rec[3], rec[4]);
           const uint4 tg = rec[5];
           es[8] = tg.x; es[9] = tg.y; es[10] = tg.z; es[11] = tg.w;
-          const uint32_t diff = open_static(st, hh, es, rs);
+          const uint32_t diff = open_static(c.st, c.hh, es, rs);
           auth = go && diff == 0u;
           if (auth) {
             peer = hs_peer(H, rs);
@@ -265,63 +188,50 @@ __global__ void __launch_bounds__(256) k_hs_open(OpenParams P) {
             o[1] = make_uint4(rs[4], rs[5], rs[6], rs[7]);
           }
           any_known = __ballot(peer != 0u) != 0ull;
-          set8(m, hh);
-          set8(m + 8, es);
-          wghs::b2s_init(st, 32u, 0u);
-          t = 64u; last = false;
+          set8(c.m, c.hh);
+          set8(c.m + 8, es);
+          wghs::b2s_init(c.st, 32u, 0u);
+          c.t = 64u; c.last = false;
           break;
         }
-        case 18: {  // ... second block: the tag
+        case OP_ES2: {  // ... second block: the tag
           const uint4 tg = rec[5];
-          m[0] = tg.x; m[1] = tg.y; m[2] = tg.z; m[3] = tg.w;
+          c.m[0] = tg.x; c.m[1] = tg.y; c.m[2] = tg.z; c.m[3] = tg.w;
 #pragma unroll
-          for (int j = 4; j < 16; ++j) m[j] = 0u;
-          t = 80u; last = true;
+          for (int j = 4; j < 16; ++j) c.m[j] = 0u;
+          c.t = 80u; c.last = true;
           break;
         }
-        case 21: {  // KDF1(ck, static-static): the extract's inner hash (a lane without a peer: over zeros, dropped)
-          uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
-          if (peer) {
-            const uint4* q = (const uint4*)(H.secrets + 32ull * (peer - 1u));
-            a = q[0];
-            b = q[1];
-          }
-          uint32_t w[8];
-          put8(w, a, b);
-          msg32(m, w);
-          set8(st, ist);
-          t = 96u; last = true;
-          break;
-        }
-        default: {  // 27: h = H(h || encrypted_timestamp), 60 bytes
+        case OP_TS: {  // h = H(h || encrypted_timestamp), 60 bytes
           const uint4 a = rec[6], b = rec[7];
-          set8(m, hh);
-          m[8] = a.x; m[9] = a.y; m[10] = a.z; m[11] = a.w; m[12] = b.x; m[13] = b.y; m[14] = b.z; m[15] = 0u;
-          wghs::b2s_init(st, 32u, 0u);
-          t = 60u; last = true;
+          set8(c.m, c.hh);
+          c.m[8] = a.x; c.m[9] = a.y; c.m[10] = a.z; c.m[11] = a.w; c.m[12] = b.x; c.m[13] = b.y; c.m[14] = b.z; c.m[15] = 0u;
+          wghs::b2s_init(c.st, 32u, 0u);
+          c.t = 60u; c.last = true;
           break;
         }
+        default: prepare(c, s, src); break;
       }
-      wghs::b2s_compress(st, m, t, last);
-      switch (step) {
-        case 0: case 18: case 27: set8(hh, st); break;
-        case 2: case 10: case 22: set8(x, st); break;  // the PRK
-        case 3: case 7: case 11: case 19: case 23: set8(ist, st); break;
-        case 4: case 8: case 12: case 20: case 24: set8(ost, st); break;
-        case 6: case 14: set8(ck, st); break;
-        case 26:
+      uint32_t next = step + 1u;
+      if (next == kOpenStaticBegin && !any_known) next = kOpenStaticEnd;  // (wave-uniform) no static-static KDF to run
+      const Step ahead = fetch(kOpenProgram, next);
+      wghs::b2s_compress(c.st, c.m, c.t, c.last);
+      switch (s.dst) {
+        case DST_CK_IF_PEER:
 #pragma unroll
-          for (int j = 0; j < 8; ++j) ck[j] = peer ? st[j] : ck[j];
+          for (int j = 0; j < 8; ++j) c.ck[j] = peer ? c.st[j] : c.ck[j];
           break;
-        default: break;
+        default: WG_HSC_PUT(c, s.dst); break;
       }
+      s = ahead;
+      step = next;
     }
     if (auth) {
       uint4* o = P.res + (size_t)kOpenResU4 * k;
-      o[2] = make_uint4(hh[0], hh[1], hh[2], hh[3]);
-      o[3] = make_uint4(hh[4], hh[5], hh[6], hh[7]);
-      o[4] = make_uint4(ck[0], ck[1], ck[2], ck[3]);
-      o[5] = make_uint4(ck[4], ck[5], ck[6], ck[7]);
+      o[2] = make_uint4(c.hh[0], c.hh[1], c.hh[2], c.hh[3]);
+      o[3] = make_uint4(c.hh[4], c.hh[5], c.hh[6], c.hh[7]);
+      o[4] = make_uint4(c.ck[0], c.ck[1], c.ck[2], c.ck[3]);
+      o[5] = make_uint4(c.ck[4], c.ck[5], c.ck[6], c.ck[7]);
       o[6] = make_uint4(peer ? peer - 1u : WG_HS_NOPEER, 0u, 0u, 0u);
     }
     if (go) st_out = auth ? (peer ? WG_HS_OPEN_OK : WG_HS_OPEN_NEWPEER) : WG_HS_OPEN_BADAUTH;
@@ -406,11 +316,6 @@ int hs_open_rekey(wg_ctx* c, HsState* t, const uint8_t* static_public) {
   return hs_peer_secrets(c, t);
 }
 
-bool hs_overlap(const void* a, uint64_t an, const void* b, uint64_t bn) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return an && bn && x < y + bn && y < x + an;
-}
-
 }  // namespace
 
 extern "C" {
@@ -493,17 +398,12 @@ int wg_hs_open(wg_ctx* c, const wg_hs_open_batch* b, void* stream) {
       (((uintptr_t)b->summary) & 7u))
     return fail(WG_EINVAL, "open_status / inits / summary must be non-NULL and aligned (4 / 16 / 8 bytes)");
   {
-    struct Range { const void* p; uint64_t bytes; };
-    const Range out[3] = {{b->open_status, 4ull * n}, {b->inits, sizeof(wg_hs_init) * (uint64_t)n}, {b->summary, sizeof(wg_hs_open_summary)}};
-    const Range in[4] = {{b->records, sizeof(wg_hs_record) * (uint64_t)n}, {b->shared, 32ull * n}, {b->dh_status, 4ull * n},
-                         {b->n_records, b->n_records ? 4u : 0u}};
-    for (int i = 0; i < 3; ++i) {
-      for (int j = i + 1; j < 3; ++j)
-        if (hs_overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes)) return fail(WG_EINVAL, "open_status, inits and summary must not overlap");
-      for (int j = 0; j < 4; ++j)
-        if (hs_overlap(out[i].p, out[i].bytes, in[j].p, in[j].bytes))
-          return fail(WG_EINVAL, "an output of wg_hs_open must not overlap records, shared, dh_status or n_records");
-    }
+    const HsRange out[3] = {{b->open_status, 4ull * n}, {b->inits, sizeof(wg_hs_init) * (uint64_t)n}, {b->summary, sizeof(wg_hs_open_summary)}};
+    const HsRange in[4] = {{b->records, sizeof(wg_hs_record) * (uint64_t)n}, {b->shared, 32ull * n}, {b->dh_status, 4ull * n},
+                           {b->n_records, b->n_records ? 4u : 0u}};
+    const int ov = hs_ranges_overlap(out, in);
+    if (ov == 1) return fail(WG_EINVAL, "open_status, inits and summary must not overlap");
+    if (ov == 2) return fail(WG_EINVAL, "an output of wg_hs_open must not overlap records, shared, dh_status or n_records");
   }
   const bool capturing = stream_capturing(s);
   int rc;

@@ -26,27 +26,33 @@
 // entry's status for itself. Waves wholly past 3 x cover exit as waves; a NOPEER or NOEPH lane, and a lane
 // past the cover, runs the dummy ladder (scalar 0, u = 9) and stores nothing.
 //
-// k_hs_resp_chain: one entry per lane, 50 BLAKE2s compressions as the steps of ONE loop around ONE
-// b2s_compress, in k_hs_open's manner: uniform switches before and after it, nothing indexed dynamically. The
-// expands of one extract share the key-block states, and T1 is the message of T2. Three things differ from
-// every HMAC of k_hs_open: KDFn(ck, "") has an empty message, so the inner hash's key block ck ^ 0x36.. is its
-// LAST block (step 39: t = 64, final); T2 and T3 hash T_{n-1} || n, 33 bytes behind the key block (t = 97);
-// and the AEAD has no ciphertext: the counter-0 chacha20_block gives the Poly1305 key, the MAC runs over
-// aad (32) || LE64(32) || LE64(0) as three Horner steps, and there is no counter-1 block. After the loop the
-// lane writes its 176-byte session to scratch and overwrites the entry's 96 bytes of ladder scratch and its
-// consumed ephemeral with zeros (plain 16-byte vector stores).
+// k_hs_resp_chain: one entry per lane, 50 BLAKE2s compressions: the steps of kRespProgram (wg_hs_chain.h),
+// written once in the order of the chain above, on the machine that k_hs_open runs on (wg_hs_chain.hip): ONE
+// loop around ONE b2s_compress, uniform switches on the step's source, operation and destination, nothing
+// indexed dynamically. The expands of one extract share the key-block states, and T1 is the message of T2.
+// What this kernel adds to the generic operations: its sources (the three ladder results) and the three
+// compressions of mac1. Three things do not occur in k_hs_open: KDFn(ck, "") has an empty message, so the
+// inner hash's key block ck ^ 0x36.. is its LAST block (OP_PAD with PAD_LAST: t = 64, final); T3 follows T2
+// (OP_TN with n = 3), each T_n hashing T_{n-1} || n, 33 bytes behind the key block (t = 97); and the AEAD has
+// no ciphertext: the counter-0 chacha20_block gives the Poly1305 key, wghc::poly_tag runs over aad (32) ||
+// LE64(32) || LE64(0), and there is no counter-1 block. The seal hangs on the one key-block step that
+// carries PAD_SEAL, the last at which x still holds k. After the loop the lane writes its 176-byte session to
+// scratch and overwrites the entry's 96 bytes of ladder scratch and its consumed ephemeral with zeros (plain
+// 16-byte vector stores).
 //
-// The loop's trip count, 50, reaches the loop through an empty asm statement, as a value the optimiser cannot
-// see. With the literal bound this loop, whose switches then depend on nothing but a counter with a known range,
-// came out of hipcc (ROCm 7.2, clang 22, -O3, gfx950) computing a wrong encrypted_empty and wrong transport keys
-// for every entry, while the same source with the bound read from a kernel argument, and a Python
-// transcription of the step table, agree with the model in all 50 steps. The cause inside the compiler was
-// not found; k_hs_open's loop is not affected (its step 19 may jump, so its trip count is not constant).
-// tests/test_gpu_hs_respond.py compares every byte, so a build that goes wrong again fails there.
+// The loop's bound is the plain constant kRespSteps. An earlier form of this loop, two switches over the step
+// counter itself with hand-numbered case lists, came out of hipcc (ROCm 7.2, clang 22, -O3, gfx950) with the
+// literal bound 50 computing a wrong encrypted_empty and wrong transport keys for every entry, and carried
+// its bound through an empty asm statement to hide it from the optimiser. The cause inside the compiler was
+// not found. In this form the switches depend on bytes loaded from the program, not on a counter of known
+// range, and the build with the constant bound passes tests/test_gpu_hs_respond.py in full; that test compares
+// every byte, so a build that goes wrong again fails there, while tests/test_hs_chain.py tells a wrong
+// program from a wrong build without a GPU.
 //
 // Constant time: no branch, address or loop bound depends on an ephemeral's value, a DH result, ck, tau, k or a
-// transport key. The two exceptions are the all-zero test of the raw ephemeral (NOEPH) and the entry's peer
-// (NOPEER); the branches depend on those statuses and on the counts alone.
+// transport key. The program is public and indexed by a public counter. The two exceptions are the all-zero
+// test of the raw ephemeral (NOEPH) and the entry's peer (NOPEER); the branches depend on the program, on
+// those statuses and on the counts alone.
 //
 // Ranks. sessions[0 .. n_ok) is the stable compaction of the OK entries, by rank_launch: k_hs_resp_chain
 // leaves the sessions in scratch and one 16-B record {ok, nopeer, noeph, 0} per 256 entries, k_rx_scan (as it
@@ -121,18 +127,7 @@ __global__ void __launch_bounds__(64) k_hs_resp_dh(RespParams P) {
 __device__ __forceinline__ void seal_empty(const uint32_t key[8], const uint32_t aad[8], uint32_t tag[4]) {
   uint32_t ks[16];
   wgd::chacha20_block(key, 0u, 0u, 0u, 0u, ks);
-  uint32_t r[5], s5[5], h[5] = {0u, 0u, 0u, 0u, 0u}, c[5];
-  wgd::poly_r_limbs(ks[0], ks[1], ks[2], ks[3], r);
-  wgd::poly_scale5(r, s5);
-#pragma unroll
-  for (int b = 0; b < 3; ++b) {
-    if (b < 2) wgd::poly_block_limbs(aad[4 * b], aad[4 * b + 1], aad[4 * b + 2], aad[4 * b + 3], 1u << 24, c);
-    else wgd::poly_block_limbs(32u, 0u, 0u, 0u, 1u << 24, c);
-#pragma unroll
-    for (int j = 0; j < 5; ++j) h[j] += c[j];
-    wgd::poly_mul<false>(h, r, s5);
-  }
-  wgd::poly_finish(h, ks[4], ks[5], ks[6], ks[7], tag);
+  wghc::poly_tag<0>(ks, aad, nullptr, tag);
 }
 
 // One entry per lane: status, and for an OK one its session to scratch; the range's counts.
@@ -154,157 +149,65 @@ __global__ void __launch_bounds__(256) k_hs_resp_chain(RespParams P) {
     const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
     const uint4* ent = (const uint4*)(P.inits + (go ? k : 0u));
     const uint4* lad = P.lad + (size_t)kLadU4 * (go ? k : 0u);
-    uint32_t hh[8], ck[8], ist[8], ost[8], x[8], st[8], m[16], tag[4] = {0u, 0u, 0u, 0u};
-    uint32_t t = 0;
-    bool last = true;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) hh[j] = ck[j] = ist[j] = ost[j] = x[j] = st[j] = 0u;
+    using namespace wghc;
+    Chain c;
+    clear(c);
+    uint32_t tag[4] = {0u, 0u, 0u, 0u};
     if (go) {
-      wgho::put8(hh, ent[5], ent[6]);
-      wgho::put8(ck, ent[7], ent[8]);
+      put8(c.hh, ent[5], ent[6]);
+      put8(c.ck, ent[7], ent[8]);
     }
     const uint32_t li = go ? P.local_index[k] : 0u;
-    uint32_t nsteps = 50u;
-    asm volatile("" : "+s"(nsteps));  // kept from the optimiser: see the file header
+    Step s = fetch(kRespProgram, 0u);
 #pragma unroll 1
-    for (uint32_t step = 0; step < nsteps; ++step) {
-      switch (step) {
-        case 0: {  // h = H(h || Epub)
-          uint32_t w[8];
-          wgho::put8(w, go ? lad[0] : z4, go ? lad[1] : z4);
-          wgho::set8(m, hh);
-          wgho::set8(m + 8, w);
-          wghs::b2s_init(st, 32u, 0u);
-          t = 64u; last = true;
-          break;
-        }
-        case 1: case 9: case 17: case 25:  // an extract's key blocks, ck ^ ipad / ck ^ opad
-          wgho::pad_block(m, ck, 0x36363636u);
-          wghs::b2s_init(st, 32u, 0u);
-          t = 64u; last = false;
-          break;
-        case 2: case 10: case 18: case 26: case 38:
-          wgho::pad_block(m, ck, 0x5C5C5C5Cu);
-          wghs::b2s_init(st, 32u, 0u);
-          t = 64u; last = false;
-          break;
-        case 3: {  // KDF1(ck, Epub): the extract's inner hash
-          uint32_t w[8];
-          wgho::put8(w, go ? lad[0] : z4, go ? lad[1] : z4);
-          wgho::msg32(m, w);
-          wgho::set8(st, ist);
-          t = 96u; last = true;
-          break;
-        }
-        case 11: {  // KDF1(ck, e E_i)
-          uint32_t w[8];
-          wgho::put8(w, go ? lad[2] : z4, go ? lad[3] : z4);
-          wgho::msg32(m, w);
-          wgho::set8(st, ist);
-          t = 96u; last = true;
-          break;
-        }
-        case 19: {  // KDF1(ck, e S_i)
-          uint32_t w[8];
-          wgho::put8(w, go ? lad[4] : z4, go ? lad[5] : z4);
-          wgho::msg32(m, w);
-          wgho::set8(st, ist);
-          t = 96u; last = true;
-          break;
-        }
-        case 27:  // KDF(ck, psk): the extract's inner hash over 32 zero bytes
-#pragma unroll
-          for (int j = 0; j < 16; ++j) m[j] = 0u;
-          wgho::set8(st, ist);
-          t = 96u; last = true;
-          break;
-        case 4: case 8: case 12: case 16: case 20: case 24: case 28: case 32: case 34: case 37: case 40: case 44:
-        case 46:  // an HMAC's outer hash over the inner digest
-          wgho::msg32(m, st);
-          wgho::set8(st, ost);
-          t = 96u; last = true;
-          break;
-        case 5: case 13: case 21: case 29: case 41:  // the expand's key blocks, PRK ^ ipad / PRK ^ opad
-          wgho::pad_block(m, x, 0x36363636u);
-          wghs::b2s_init(st, 32u, 0u);
-          t = 64u; last = false;
-          break;
-        case 6: case 14: case 22: case 30: case 42:
-          wgho::pad_block(m, x, 0x5C5C5C5Cu);
-          wghs::b2s_init(st, 32u, 0u);
-          t = 64u; last = false;
-          break;
-        case 7: case 15: case 23: case 31: case 43:  // T1 = HMAC(PRK, 0x01): inner
-#pragma unroll
-          for (int j = 0; j < 16; ++j) m[j] = j == 0 ? 1u : 0u;
-          wgho::set8(st, ist);
-          t = 65u; last = true;
-          break;
-        case 33: case 45:  // T2 = HMAC(PRK, T1 || 0x02): inner (T1 is in ck)
-          wgho::msg32(m, ck);
-          m[8] = 2u;
-          wgho::set8(st, ist);
-          t = 97u; last = true;
-          break;
-        case 35:  // h = H(h || tau) (tau is in x)
-          wgho::set8(m, hh);
-          wgho::set8(m + 8, x);
-          wghs::b2s_init(st, 32u, 0u);
-          t = 64u; last = true;
-          break;
-        case 36:  // T3 = HMAC(PRK, T2 || 0x03): inner (T2 = tau)
-          wgho::msg32(m, x);
-          m[8] = 3u;
-          wgho::set8(st, ist);
-          t = 97u; last = true;
-          break;
-        case 39:  // KDF(ck, ""): the extract's inner hash is its key block alone, the LAST block
-          wgho::pad_block(m, ck, 0x36363636u);
-          wghs::b2s_init(st, 32u, 0u);
-          t = 64u; last = true;
-          break;
-        case 47: {  // the mac1 key, H("mac1----" || S_i): 40 bytes
-          uint32_t w[8];
-          wgho::put8(w, go ? ent[3] : z4, go ? ent[4] : z4);
-          m[0] = 0x3163616Du;
-          m[1] = 0x2D2D2D2Du;
-          wgho::set8(m + 2, w);
-#pragma unroll
-          for (int j = 10; j < 16; ++j) m[j] = 0u;
-          wghs::b2s_init(st, 32u, 0u);
-          t = 40u; last = true;
-          break;
-        }
-        case 48:  // mac1 = BLAKE2s-128 under that key (in ist): the key block
-          wgho::msg32(m, ist);
-          wghs::b2s_init(st, 16u, 32u);
-          t = 64u; last = false;
-          break;
-        default: {  // 49: ... and response[0 .. 60)
-          uint32_t w[8];
-          wgho::put8(w, go ? lad[0] : z4, go ? lad[1] : z4);
-          m[0] = 2u;
-          m[1] = li;
-          m[2] = go ? ent[0].z : 0u;
-          wgho::set8(m + 3, w);
-          m[11] = tag[0]; m[12] = tag[1]; m[13] = tag[2]; m[14] = tag[3];
-          m[15] = 0u;
-          t = 124u; last = true;
-          break;
-        }
+    for (uint32_t step = 0; step < kRespSteps; ++step) {
+      uint32_t src[8];
+      switch (s.arg) {
+        case SRC_EPUB: put8(src, go ? lad[0] : z4, go ? lad[1] : z4); break;
+        case SRC_EE: put8(src, go ? lad[2] : z4, go ? lad[3] : z4); break;
+        case SRC_ES: put8(src, go ? lad[4] : z4, go ? lad[5] : z4); break;
+        default: source(c, s.arg, src); break;
       }
-      // x = k (step 37's T3): the seal of nothing under it, before the transport keys' KDF takes x
-      if (step == 38u) seal_empty(x, hh, tag);
-      wghs::b2s_compress(st, m, t, last);
-      switch (step) {
-        case 0: case 35: wgho::set8(hh, st); break;
-        case 4: case 12: case 20: case 28: case 40: wgho::set8(x, st); break;  // the PRK
-        case 1: case 9: case 17: case 25: case 5: case 13: case 21: case 29: case 41: case 47: wgho::set8(ist, st); break;
-        case 2: case 10: case 18: case 26: case 38: case 6: case 14: case 22: case 30: case 42: wgho::set8(ost, st); break;
-        case 8: case 16: case 24: case 32: case 44: wgho::set8(ck, st); break;  // T1: the next ck; recv_key
-        case 34: case 37: case 46: wgho::set8(x, st); break;  // tau; k; send_key
-        default: break;
+      switch (s.op) {
+        case OP_MAC1KEY: {  // the mac1 key, H("mac1----" || S_i): 40 bytes
+          uint32_t w[8];
+          put8(w, go ? ent[3] : z4, go ? ent[4] : z4);
+          c.m[0] = 0x3163616Du;
+          c.m[1] = 0x2D2D2D2Du;
+          set8(c.m + 2, w);
+#pragma unroll
+          for (int j = 10; j < 16; ++j) c.m[j] = 0u;
+          wghs::b2s_init(c.st, 32u, 0u);
+          c.t = 40u; c.last = true;
+          break;
+        }
+        case OP_MAC1A:  // mac1 = BLAKE2s-128 under that key (in ist): the key block
+          msg32(c.m, c.ist);
+          wghs::b2s_init(c.st, 16u, 32u);
+          c.t = 64u; c.last = false;
+          break;
+        case OP_MAC1B: {  // ... and response[0 .. 60)
+          uint32_t w[8];
+          put8(w, go ? lad[0] : z4, go ? lad[1] : z4);
+          c.m[0] = 2u;
+          c.m[1] = li;
+          c.m[2] = go ? ent[0].z : 0u;
+          set8(c.m + 3, w);
+          c.m[11] = tag[0]; c.m[12] = tag[1]; c.m[13] = tag[2]; c.m[14] = tag[3];
+          c.m[15] = 0u;
+          c.t = 124u; c.last = true;
+          break;
+        }
+        default:
+          // the flagged key block: x = k, the seal of nothing under it, before the transport keys' KDF takes x
+          if (s.op == OP_PAD && (s.imm & PAD_SEAL)) seal_empty(c.x, c.hh, tag);
+          prepare(c, s, src);
+          break;
       }
+      const Step ahead = fetch(kRespProgram, step + 1u);
+      wghs::b2s_compress(c.st, c.m, c.t, c.last);
+      WG_HSC_PUT(c, s.dst);
+      s = ahead;
     }
     if (go) {
       const uint4 q0 = ent[0];  // {index, record, sender_index, peer}
@@ -314,13 +217,13 @@ __global__ void __launch_bounds__(256) k_hs_resp_chain(RespParams P) {
       o[1] = make_uint4(2u, li, q0.z, a.x);
       o[2] = make_uint4(a.y, a.z, a.w, b.x);
       o[3] = make_uint4(b.y, b.z, b.w, tag[0]);
-      o[4] = make_uint4(tag[1], tag[2], tag[3], st[0]);
-      o[5] = make_uint4(st[1], st[2], st[3], 0u);
+      o[4] = make_uint4(tag[1], tag[2], tag[3], c.st[0]);
+      o[5] = make_uint4(c.st[1], c.st[2], c.st[3], 0u);
       o[6] = make_uint4(0u, 0u, 0u, q0.z);
-      o[7] = make_uint4(x[0], x[1], x[2], x[3]);
-      o[8] = make_uint4(x[4], x[5], x[6], x[7]);
-      o[9] = make_uint4(ck[0], ck[1], ck[2], ck[3]);
-      o[10] = make_uint4(ck[4], ck[5], ck[6], ck[7]);
+      o[7] = make_uint4(c.x[0], c.x[1], c.x[2], c.x[3]);
+      o[8] = make_uint4(c.x[4], c.x[5], c.x[6], c.x[7]);
+      o[9] = make_uint4(c.ck[0], c.ck[1], c.ck[2], c.ck[3]);
+      o[10] = make_uint4(c.ck[4], c.ck[5], c.ck[6], c.ck[7]);
       // the ladders' results and the ephemeral are spent
       uint4* wl = P.lad + (size_t)kLadU4 * k;
 #pragma unroll
@@ -381,18 +284,12 @@ int wg_hs_respond(wg_ctx* c, const wg_hs_respond_batch* b, void* stream) {
       (((uintptr_t)b->summary) & 7u))
     return fail(WG_EINVAL, "resp_status / sessions / summary must be non-NULL and aligned (4 / 16 / 8 bytes)");
   {
-    struct Range { const void* p; uint64_t bytes; };
-    const Range out[4] = {{b->ephemerals, 32ull * n}, {b->resp_status, 4ull * n}, {b->sessions, sizeof(wg_hs_session) * (uint64_t)n},
-                          {b->summary, sizeof(wg_hs_respond_summary)}};
-    const Range in[3] = {{b->inits, sizeof(wg_hs_init) * (uint64_t)n}, {b->local_index, 4ull * n}, {b->n_inits, b->n_inits ? 4u : 0u}};
-    for (int i = 0; i < 4; ++i) {
-      for (int j = i + 1; j < 4; ++j)
-        if (hs_overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes))
-          return fail(WG_EINVAL, "ephemerals, resp_status, sessions and summary must not overlap");
-      for (int j = 0; j < 3; ++j)
-        if (hs_overlap(out[i].p, out[i].bytes, in[j].p, in[j].bytes))
-          return fail(WG_EINVAL, "an output of wg_hs_respond must not overlap inits, local_index or n_inits");
-    }
+    const HsRange out[4] = {{b->ephemerals, 32ull * n}, {b->resp_status, 4ull * n}, {b->sessions, sizeof(wg_hs_session) * (uint64_t)n},
+                            {b->summary, sizeof(wg_hs_respond_summary)}};
+    const HsRange in[3] = {{b->inits, sizeof(wg_hs_init) * (uint64_t)n}, {b->local_index, 4ull * n}, {b->n_inits, b->n_inits ? 4u : 0u}};
+    const int ov = hs_ranges_overlap(out, in);
+    if (ov == 1) return fail(WG_EINVAL, "ephemerals, resp_status, sessions and summary must not overlap");
+    if (ov == 2) return fail(WG_EINVAL, "an output of wg_hs_respond must not overlap inits, local_index or n_inits");
   }
   const bool capturing = stream_capturing(s);
   int rc;
