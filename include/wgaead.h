@@ -868,6 +868,134 @@ typedef struct wg_hs_respond_batch {
 } wg_hs_respond_batch;
 int wg_hs_respond(wg_ctx* ctx, const wg_hs_respond_batch* batch, void* stream);
 
+/* ---- the initiator's side, on the device ----
+ * A node that restarts, or whose sessions expire together, initiates to every peer that has an endpoint
+ * (SessionManager.attemptInitiatorHandshake, SessionManager.java:170-207). wg_hs_initiate is InitiatorStageOne's
+ * constructor and OutgoingInitiation (Handshakes.java:77-117, OutgoingInitiation.java:22-38,
+ * InitiationPacket.java:110-120) over a batch; wg_hs_finish is consumeMessageResponse (Handshakes.java:119-151)
+ * over wg_hs_check's records on the initiator's context. Both bit-exact. With H, KDFn, CK0, H0 as above, S the
+ * static private key, S_pub its public key, S_r = the peer's static public key in wg_hs_peers_set's table, ss_r =
+ * that table's stored X25519(S, S_r), e = the ephemeral:
+ *     Epub = X25519(e, 9)       h = H(H(H0 || S_r) || Epub)        ck = KDF1(CK0, Epub)
+ *     es = X25519(e, S_r)       k = KDF2(ck, es)   ck = KDF1(ck, es)
+ *     enc_static = ChaCha20-Poly1305-seal(k, nonce 0^12, aad = h, S_pub)   (48 B)     h = H(h || enc_static)
+ *     k = KDF2(ck, ss_r)        ck = KDF1(ck, ss_r)
+ *     enc_ts = ChaCha20-Poly1305-seal(k, nonce 0^12, aad = h, timestamp)   (28 B)     h = H(h || enc_ts)
+ *     msg = {1, 0,0,0, LE32(local_index), Epub, enc_static, enc_ts,
+ *            mac1 = BLAKE2s-128(key = H("mac1----" || S_r), msg[0 .. 116)), mac2 = 0^16}
+ *   and for a response with E_r = msg[12 .. 44), h / ck / e from the pending entry, psk = the peer's:
+ *     h = H(h || E_r)     ck = KDF1(ck, E_r)     ck = KDF1(ck, X25519(e, E_r))     ck = KDF1(ck, X25519(S, E_r))
+ *     tau = KDF2(ck, psk)   k = KDF3(ck, psk)   ck = KDF1(ck, psk)       h = H(h || tau)
+ *     the Poly1305 tag of (aad = h, no ciphertext) under k, nonce 0^12, must equal msg[44 .. 60)
+ *     send_key = KDF1(ck, "")      recv_key = KDF2(ck, "")            (:147: the initiator sends with T1)
+ *
+ * wg_hs_psks_set(ctx, psks, n): the peers' preshared keys (connectionInfo.presharedKey(), SessionManager.java:172;
+ *   host pointer, 32 n bytes, by position in the peer table). n must equal the table's count, else WG_EINVAL.
+ *   wg_hs_peers_set resets every psk to 32 zero bytes. Synchronous, and ordered after everything queued before
+ *   it. The psks sit behind a header at a fixed device address: a captured finish sees new psks without
+ *   re-capture. wg_ctx_destroy wipes them. The reference's responder, and wg_hs_respond, use the zero psk
+ *   (Handshakes.java:262): only a zero-psk initiator interoperates with them.
+ *
+ * wg_hs_initiate(ctx, b, stream): for every k < n, in this order:
+ *   1. peer[k] >= the table's count: WG_HS_INIT_BADPEER. 2. the 32 bytes ephemerals[32 k ..) are all zero,
+ *   tested before clamping: WG_HS_INIT_NOEPH. 3. WG_HS_INIT_OK. Both failures are the caller's own mistakes,
+ *   not traffic: the outputs are aligned to position, not compacted. status[k]; records[k] = {index = k, len =
+ *   148, msg, _pad = 0} (what wg_hs_dh and wg_hs_open read), 160 zero bytes for a non-OK entry; pending[k] =
+ *   {state = 1, peer, local_index, 0, ephemeral = the raw private key, hash = the final h, chain_key = the final
+ *   ck}, 112 zero bytes for a non-OK entry; summary = {n_ok, n_badpeer, n_noeph, 0}. Every byte of every output
+ *   up to n is defined, nothing behind n is touched. ephemerals (fresh private keys from the host's CSPRNG,
+ *   clamped on the device) is input AND output: an OK entry's 32 bytes are zeroed, the others left alone, so a
+ *   replayed graph without fresh keys initiates nothing (all NOEPH). timestamps: 12 bytes each, the host's
+ *   TAI64N. n = 0 is a no-op. Without a private key: WG_ENOKEY. n above 2^30: WG_E2BIG. ephemerals, records,
+ *   pending: 16-byte aligned; summary: 8; the others: 4. An output (ephemerals among them) that overlaps another
+ *   output or an input: WG_EINVAL. Scratch (64 bytes per entry, holding the ladders' results only for the time
+ *   of the call) is sized by wg_hs_reserve; a call that needs more allocates it, except on a capturing stream
+ *   (WG_EINVAL: reserve first); wg_ctx_destroy wipes it. Three launches (ladders, chain, scan). The two ladders
+ *   of an entry run in two neighbouring lanes.
+ *
+ * wg_hs_finish(ctx, b, stream): for every k < min(*n_records, n) (n_records as in wg_hs_dh; NULL: all n), in this
+ *   order: 1. records[k].len == 148: WG_HS_FIN_SKIPPED (an initiation). 2. len != 92: WG_HS_FIN_BADDESC. 3. no
+ *   live pending entry (state == 1 and peer below the table's count) has local_index == msg[8 .. 12):
+ *   WG_HS_FIN_NOPENDING; if several live entries share a local_index, the lowest position is the one found.
+ *   4. the tag does not verify (all 16 bytes compared, no early exit): WG_HS_FIN_BADAUTH. 5. WG_HS_FIN_OK.
+ *   fin_status[k] is written for the covered k and nothing behind them. established[0 .. n_ok) is the stable
+ *   compaction of the OK records: {index = records[k].index, record = k, pending = the entry's position, peer,
+ *   local_index, remote_index = msg[4 .. 8), 0, 0, send_key, recv_key}; nothing behind n_ok entries is touched.
+ *   summary = {n_ok, n_nopending, n_badauth, n_skipped}. pending (n_pending entries) is input AND output: an OK
+ *   record's entry is overwritten with zeros, so a replayed response, or a replayed graph, finds nothing
+ *   (NOPENDING); a BADAUTH record leaves its entry byte for byte as it was (mac1 needs only the public key: a
+ *   forger must not be able to cancel a handshake). If two records of one call authenticate against the same
+ *   pending entry, both are emitted, in record order and with the same `pending` field; the host keeps the
+ *   first. n = 0 is a no-op. Without a private key: WG_ENOKEY. n above 2^30 or n_pending above 2^28: WG_E2BIG.
+ *   records, pending, established: 16-byte aligned; summary: 8; the others: 4. An output (pending among them)
+ *   that overlaps another output or an input: WG_EINVAL. The receiver index is matched on the device: an
+ *   open-addressing table of pending positions in scratch (the smallest power of two >= max(16, 4 n_pending)
+ *   words), filled and built by the call's first two launches; the lowest position wins a shared local_index.
+ *   Scratch (160 bytes per record, 16 per pending entry) by wg_hs_reserve(max(n, n_pending)), as above. Six
+ *   launches (fill, insert, ladders, chain, scan, emit; the emit zeroes the consumed entries), no wait between workgroups, nothing about a
+ *   call on the host: a captured check + finish replays.
+ *   For both calls: no branch, address or loop bound depends on an ephemeral's value, a DH result, ck, tau, k, a
+ *   psk's value or a transport key, except the all-zero test of the raw ephemeral; the receiver index and the
+ *   peer position are public. The host installs send_key / recv_key with wg_keys_set and local_index with
+ *   wg_rx_sessions_set. */
+#define WG_HS_INIT_OK 0u
+#define WG_HS_INIT_BADPEER 1u /* peer[k] is not a position in the peer table */
+#define WG_HS_INIT_NOEPH 2u   /* the entry's ephemeral is all zero */
+#define WG_HS_FIN_OK 0u
+#define WG_HS_FIN_NOPENDING 1u /* no live pending entry has the response's receiver index */
+#define WG_HS_FIN_BADAUTH 2u
+#define WG_HS_FIN_SKIPPED 3u /* an initiation */
+#define WG_HS_FIN_BADDESC 4u /* any other record length */
+typedef struct wg_hs_pending { /* 112 bytes */
+  uint32_t state;       /* 1: live, 0: empty */
+  uint32_t peer;        /* position in wg_hs_peers_set's table */
+  uint32_t local_index; /* the sender index of the initiation */
+  uint32_t _zero;
+  uint8_t ephemeral[32]; /* the raw ephemeral private key */
+  uint8_t hash[32];
+  uint8_t chain_key[32];
+} wg_hs_pending;
+typedef struct wg_hs_established { /* 96 bytes */
+  uint32_t index;        /* batch index of the response's datagram */
+  uint32_t record;       /* position in wg_hs_check's records */
+  uint32_t pending;      /* position in pending */
+  uint32_t peer;
+  uint32_t local_index;  /* the initiator's session index: msg[8 .. 12) */
+  uint32_t remote_index; /* the responder's: msg[4 .. 8) */
+  uint32_t _zero[2];
+  uint8_t send_key[32];
+  uint8_t recv_key[32];
+} wg_hs_established;
+typedef struct wg_hs_initiate_summary {
+  uint32_t n_ok, n_badpeer, n_noeph, _zero;
+} wg_hs_initiate_summary;
+typedef struct wg_hs_initiate_batch {
+  const uint32_t* peer;            /* device, n entries */
+  uint8_t* ephemerals;             /* device, 16-byte aligned, n * 32 bytes; in and out */
+  const uint8_t* timestamps;       /* device, 4-byte aligned, n * 12 bytes */
+  const uint32_t* local_index;     /* device, n entries */
+  uint32_t* status;                /* device, n entries, WG_HS_INIT_* */
+  wg_hs_record* records;           /* device, 16-byte aligned, n entries */
+  wg_hs_pending* pending;          /* device, 16-byte aligned, n entries */
+  wg_hs_initiate_summary* summary; /* device, 16 bytes, 8-byte aligned */
+  uint32_t n, _reserved;
+} wg_hs_initiate_batch;
+typedef struct wg_hs_finish_summary {
+  uint32_t n_ok, n_nopending, n_badauth, n_skipped;
+} wg_hs_finish_summary;
+typedef struct wg_hs_finish_batch {
+  const wg_hs_record* records;    /* device, 16-byte aligned: wg_hs_check's records */
+  const uint32_t* n_records;      /* device: &wg_hs_summary.n_valid; NULL: all n */
+  wg_hs_pending* pending;         /* device, 16-byte aligned, n_pending entries; in and out */
+  uint32_t* fin_status;           /* device, n entries, WG_HS_FIN_* */
+  wg_hs_established* established; /* device, 16-byte aligned, n entries */
+  wg_hs_finish_summary* summary;  /* device, 16 bytes, 8-byte aligned */
+  uint32_t n, n_pending;
+} wg_hs_finish_batch;
+int wg_hs_psks_set(wg_ctx* ctx, const uint8_t* psks_host /* 32 n bytes */, uint32_t n);
+int wg_hs_initiate(wg_ctx* ctx, const wg_hs_initiate_batch* batch, void* stream);
+int wg_hs_finish(wg_ctx* ctx, const wg_hs_finish_batch* batch, void* stream);
+
 int wg_seal1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* pt, uint32_t len, uint8_t* out);
 int wg_open1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* in, uint32_t len, uint8_t* pt);
 int wg_pp_config(wg_ctx* ctx, uint32_t waves, uint32_t idle_us);

@@ -66,6 +66,14 @@ WG_HS_RESP_OK = 0
 WG_HS_RESP_NOPEER = 1
 WG_HS_RESP_NOEPH = 2
 WG_HS_RESP_SKIP_NEWPEER = 1
+WG_HS_INIT_OK = 0
+WG_HS_INIT_BADPEER = 1
+WG_HS_INIT_NOEPH = 2
+WG_HS_FIN_OK = 0
+WG_HS_FIN_NOPENDING = 1
+WG_HS_FIN_BADAUTH = 2
+WG_HS_FIN_SKIPPED = 3
+WG_HS_FIN_BADDESC = 4
 WG_MAX_FILTERS = 65536
 WG_NO_FILTER = 0xFFFFFFFF
 WG_LEN_INVALID = 0xFFFFFFFF
@@ -235,6 +243,35 @@ class WgHsRespondBatch(ctypes.Structure):
                 ("summary", ctypes.c_void_p), ("n", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
+class WgHsPending(ctypes.Structure):
+    """wg_hs_pending: one initiation awaiting its response (wg_hs_initiate, wg_hs_finish)."""
+    _fields_ = [("state", ctypes.c_uint32), ("peer", ctypes.c_uint32), ("local_index", ctypes.c_uint32),
+                ("_zero", ctypes.c_uint32), ("ephemeral", ctypes.c_uint8 * 32), ("hash", ctypes.c_uint8 * 32),
+                ("chain_key", ctypes.c_uint8 * 32)]
+
+
+class WgHsEstablished(ctypes.Structure):
+    """wg_hs_established: one completed handshake of wg_hs_finish."""
+    _fields_ = [("index", ctypes.c_uint32), ("record", ctypes.c_uint32), ("pending", ctypes.c_uint32),
+                ("peer", ctypes.c_uint32), ("local_index", ctypes.c_uint32), ("remote_index", ctypes.c_uint32),
+                ("_zero", ctypes.c_uint32 * 2), ("send_key", ctypes.c_uint8 * 32), ("recv_key", ctypes.c_uint8 * 32)]
+
+
+class WgHsInitiateBatch(ctypes.Structure):
+    """wg_hs_initiate_batch: one wg_hs_initiate call (device pointers)."""
+    _fields_ = [("peer", ctypes.c_void_p), ("ephemerals", ctypes.c_void_p), ("timestamps", ctypes.c_void_p),
+                ("local_index", ctypes.c_void_p), ("status", ctypes.c_void_p), ("records", ctypes.c_void_p),
+                ("pending", ctypes.c_void_p), ("summary", ctypes.c_void_p), ("n", ctypes.c_uint32),
+                ("_reserved", ctypes.c_uint32)]
+
+
+class WgHsFinishBatch(ctypes.Structure):
+    """wg_hs_finish_batch: one wg_hs_finish call (device pointers)."""
+    _fields_ = [("records", ctypes.c_void_p), ("n_records", ctypes.c_void_p), ("pending", ctypes.c_void_p),
+                ("fin_status", ctypes.c_void_p), ("established", ctypes.c_void_p), ("summary", ctypes.c_void_p),
+                ("n", ctypes.c_uint32), ("n_pending", ctypes.c_uint32)]
+
+
 class WgCompletion(ctypes.Structure):
     """wg_completion: one reaped packet of a wg_queue."""
     _fields_ = [("user", ctypes.c_uint64), ("counter", ctypes.c_uint64), ("data", ctypes.c_void_p),
@@ -308,6 +345,9 @@ SIGNATURES = [
     ("wg_hs_peers_set", _I, [_VP, _VP, _U32]),
     ("wg_hs_open", _I, [_VP, ctypes.POINTER(WgHsOpenBatch), _VP]),
     ("wg_hs_respond", _I, [_VP, ctypes.POINTER(WgHsRespondBatch), _VP]),
+    ("wg_hs_psks_set", _I, [_VP, _VP, _U32]),
+    ("wg_hs_initiate", _I, [_VP, ctypes.POINTER(WgHsInitiateBatch), _VP]),
+    ("wg_hs_finish", _I, [_VP, ctypes.POINTER(WgHsFinishBatch), _VP]),
     ("wg_seal1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_open1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_pp_config", _I, [_VP, _U32, _U32]),

@@ -44,8 +44,15 @@ struct HsPeerHdr {  // at a fixed device address; wg_hs_peers_set rewrites it (a
 
 __host__ __device__ inline uint32_t hs_peer_bucket(uint32_t w0, uint32_t w1) { return mix32(w0 ^ mix32(w1)); }
 
+struct HsPskHdr {  // at a fixed device address; wg_hs_peers_set and wg_hs_psks_set rewrite it: wg_hs_initiate.hip
+  const uint8_t* psks;  // 32 B per peer: the preshared keys, in the peer table's order
+  uint32_t count, _pad;
+};
+
 struct HsState {
-  DevBuf d_key;    // [0, 32) the mac1 key, [32, 64) H(H0 || static public key) (wg_hs_static_set) (fixed address)
+  // [0, 32) the mac1 key, [32, 64) H(H0 || static public key), [64, 96) the static public key (wg_hs_static_set)
+  // (fixed address)
+  DevBuf d_key;
   DevBuf d_priv;   // the static private key, 32 B (fixed address; wg_hs_static_set, wg_x25519.hip)
   DevBuf d_stage;  // wg_hs_key_set: descriptor, "mac1----" || public key, status; wg_hs_static_set: [128, 196), [256, 356)
   DevBuf d_part;   // per range of 256 list positions: {valid, init, resp, rejected}, then their exclusive prefixes
@@ -55,6 +62,10 @@ struct HsState {
   DevBuf d_phdr, d_pempty, d_pslots, d_pin, d_psec, d_pdesc, d_ores, d_opart;
   // wg_hs_respond.hip: per entry the three ladders' results (96 B) and the session (176 B), per range its counts
   DevBuf d_rlad, d_rres, d_rpart;
+  // wg_hs_initiate.hip: the psks' header (fixed address) and the psks; per entry or record the two ladders' results
+  // (64 B), per range its counts; wg_hs_finish's established entries (96 B per record) and its table of pending
+  // positions
+  DevBuf d_pskhdr, d_ppsk, d_ilad, d_ipart, d_fres, d_ftab;
   uint32_t n_peers = 0;
   bool has_key = false;
   bool has_priv = false;
@@ -64,21 +75,26 @@ struct HsState {
 const PlanWords kHsCheckWords{"handshake check", "datagrams", "wg_hs_reserve"};
 const PlanWords kHsOpenWords{"handshake open", "records", "wg_hs_reserve"};
 const PlanWords kHsRespWords{"handshake respond", "entries", "wg_hs_reserve"};
+const PlanWords kHsInitWords{"handshake initiate", "entries", "wg_hs_reserve"};
+const PlanWords kHsFinWords{"handshake finish", "records", "wg_hs_reserve"};
 
 // The handshake state, allocated at the first wg_hs_* call. Caller holds c->mu.
 int hs_get(wg_ctx* c, HsState** out) {
   if (!c->hs) {
     auto t = std::make_unique<HsState>();
     int rc;
-    if ((rc = t->d_key.ensure(64)) != WG_OK || (rc = t->d_priv.ensure(32)) != WG_OK ||
+    if ((rc = t->d_key.ensure(96)) != WG_OK || (rc = t->d_priv.ensure(32)) != WG_OK ||
         (rc = t->d_stage.ensure(512)) != WG_OK || (rc = t->d_phdr.ensure(sizeof(HsPeerHdr))) != WG_OK ||
-        (rc = t->d_pempty.ensure(16 * sizeof(uint32_t))) != WG_OK)
+        (rc = t->d_pempty.ensure(16 * sizeof(uint32_t))) != WG_OK || (rc = t->d_pskhdr.ensure(sizeof(HsPskHdr))) != WG_OK)
       return rc;
     HsPeerHdr H{};  // no peers
     H.slots = (const uint32_t*)t->d_pempty.p;
     H.mask = 15u;
+    HsPskHdr K{};  // ... and no psks
+    K.psks = (const uint8_t*)t->d_pempty.p;
     hipError_t e = t->order.create();
-    if (e == hipSuccess) e = hipMemsetAsync(t->d_key.p, 0, 64, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_key.p, 0, 96, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(t->d_pskhdr.p, &K, sizeof K, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(t->d_priv.p, 0, 32, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(t->d_pempty.p, 0, 16 * sizeof(uint32_t), c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(t->d_phdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream);
@@ -95,10 +111,11 @@ void hs_free(wg_ctx* c) {
   HsState* t = c->hs;
   if (t->d_key.p) {  // the keys are wiped, like the key table
     (void)hipDeviceSynchronize();
-    (void)hipMemsetAsync(t->d_key.p, 0, 64, c->stream);
+    (void)hipMemsetAsync(t->d_key.p, 0, 96, c->stream);
     if (t->d_priv.p) (void)hipMemsetAsync(t->d_priv.p, 0, 32, c->stream);
-    // the peers' static-static secrets, what the last open derived from them, and the last respond's scratch
-    for (DevBuf* b : {&t->d_psec, &t->d_pin, &t->d_ores, &t->d_rlad, &t->d_rres})
+    // the peers' static-static secrets, what the last open derived from them, and the last respond's scratch; the
+    // psks and the last initiate's and finish's scratch
+    for (DevBuf* b : {&t->d_psec, &t->d_pin, &t->d_ores, &t->d_rlad, &t->d_rres, &t->d_ppsk, &t->d_ilad, &t->d_fres})
       if (b->p) (void)hipMemsetAsync(b->p, 0, b->cap, c->stream);
     (void)hipStreamSynchronize(c->stream);
   }
@@ -133,6 +150,29 @@ int hs_resp_grow(HsState* t, uint32_t n) {
     if (b->p) HIPTRY(hipMemset(b->p, 0, b->cap));
   if ((rc = t->d_rpart.ensure((size_t)std::max(rank_blocks(n), 1u) * 16)) != WG_OK || (rc = t->d_rlad.ensure(m * 96)) != WG_OK) return rc;
   return t->d_rres.ensure(m * 176);
+}
+
+// the scratch of wg_hs_initiate for n entries and of wg_hs_finish for n records against n_pending entries (64 + 96 B
+// per item, per range its counts, the table of pending positions), and its growth
+uint32_t hs_fin_capacity(uint32_t n_pending) {
+  uint32_t cap = 16;
+  while ((uint64_t)cap < 4ull * n_pending) cap <<= 1;
+  return cap;
+}
+bool hs_init_fits(const HsState* t, uint32_t n, uint32_t n_pending) {
+  const size_t m = std::max(n, 1u);
+  return (size_t)std::max(rank_blocks(n), 1u) * 16 <= t->d_ipart.cap && m * 64 <= t->d_ilad.cap && m * 96 <= t->d_fres.cap &&
+         (size_t)hs_fin_capacity(n_pending) * 4 <= t->d_ftab.cap;
+}
+int hs_init_grow(HsState* t, uint32_t n, uint32_t n_pending) {
+  const size_t m = std::max(n, 1u);
+  int rc;
+  for (DevBuf* b : {&t->d_ilad, &t->d_fres})  // freed when they grow: wiped first
+    if (b->p) HIPTRY(hipMemset(b->p, 0, b->cap));
+  if ((rc = t->d_ipart.ensure((size_t)std::max(rank_blocks(n), 1u) * 16)) != WG_OK || (rc = t->d_ilad.ensure(m * 64)) != WG_OK ||
+      (rc = t->d_fres.ensure(m * 96)) != WG_OK)
+    return rc;
+  return t->d_ftab.ensure((size_t)hs_fin_capacity(n_pending) * 4);
 }
 
 int hs_begin(HsState* t, hipStream_t s, bool capturing, uint32_t n, bool open, const PlanWords& w) {
@@ -496,9 +536,11 @@ int wg_hs_reserve(wg_ctx* c, uint32_t max_messages) {
   HsState* t;
   int rc;
   if ((rc = hs_get(c, &t)) != WG_OK) return rc;
-  return plan_reserve(hs_scratch_fits(t, max_messages, true) && hs_resp_fits(t, max_messages), [&] {
-    const int grc = hs_scratch_grow(t, max_messages, true);
-    return grc != WG_OK ? grc : hs_resp_grow(t, max_messages);
+  const uint32_t pend = std::min(max_messages, 0x10000000u);  // (wg_hs_finish takes no more pending entries)
+  return plan_reserve(hs_scratch_fits(t, max_messages, true) && hs_resp_fits(t, max_messages) && hs_init_fits(t, max_messages, pend), [&] {
+    int grc = hs_scratch_grow(t, max_messages, true);
+    if (grc == WG_OK) grc = hs_resp_grow(t, max_messages);
+    return grc != WG_OK ? grc : hs_init_grow(t, max_messages, pend);
   });
 }
 

@@ -1,8 +1,9 @@
-// wg_hs_chain.h — the two Noise chains of the responder's handshake as data: the step record, its enums, the
-// builders and the programs of k_hs_open (wg_hs_open.hip) and k_hs_resp_chain (wg_hs_respond.hip). Included by
-// wg_hs_chain.hip, which holds the machine that runs them. A host compiler reads this file too:
-// tests/test_hs_chain.py prints both programs and runs them through a Python interpreter of the operations
-// against the models, so a wrong table fails without a GPU.
+// wg_hs_chain.h — the Noise chains of the handshake as data: the step record, its enums, the builders and the
+// programs of k_hs_open (wg_hs_open.hip), k_hs_resp_chain (wg_hs_respond.hip) and the initiator's k_hs_init_chain
+// and k_hs_fin_chain (wg_hs_initiate.hip). Included by wg_hs_chain.hip, which holds the machine that runs them. A
+// host compiler reads this file too: tests/test_hs_chain.py and tests/test_hs_initiate.py print the programs and
+// run them through a Python interpreter of the operations against the models, so a wrong table fails without a
+// GPU.
 //
 // A step is one BLAKE2s compression: `op` says what is hashed, `arg` names the 32 bytes it takes (SRC_*), `imm`
 // is the operation's small constant, `dst` says where the eight state words go afterwards. The programs are
@@ -39,6 +40,13 @@ enum Op : uint8_t {
   OP_MAC1KEY,  // H("mac1----" || S_i)
   OP_MAC1A,    // BLAKE2s-128 under that key (in ist): the key block
   OP_MAC1B,    // ... and response[0 .. 60)
+  // k_hs_init_chain's own (it has its own OP_MAC1KEY and OP_MAC1A too: the key is the peer's)
+  OP_IH0,     // H(H0 || S_r)
+  OP_IES1,    // the AEAD seal of S_pub under st; H(h || encrypted_static), first block
+  OP_IES2,    // ... its second block: the tag
+  OP_ITS,     // the AEAD seal of the timestamp under st; H(h || encrypted_timestamp)
+  OP_IMAC1B,  // mac1's message, initiation[0 .. 64)
+  OP_IMAC1C,  // ... and initiation[64 .. 116)
 };
 
 enum Src : uint8_t {
@@ -52,14 +60,18 @@ enum Src : uint8_t {
   // k_hs_resp_chain's: the three ladder results
   SRC_EPUB,
   SRC_EE,
-  SRC_ES,
+  SRC_ES,  // (k_hs_init_chain: e S_r; k_hs_fin_chain: S E_r)
+  // k_hs_fin_chain's: the response's ephemeral and the peer's preshared key (its ladder results are SRC_EE, SRC_ES)
+  SRC_ER,
+  SRC_PSK,
 };
 
 enum Imm : uint8_t {
   PAD_IPAD = 0,
   PAD_OPAD = 1,
   PAD_LAST = 2,   // the key block is the whole message: KDF(ck, "")
-  PAD_SEAL = 128, // k_hs_resp_chain: seal_empty(x, h) before this step, while x still holds k
+  PAD_SEAL = 128, // k_hs_resp_chain: seal_empty(x, h) before this step, while x still holds k (k_hs_fin_chain: the
+                  // same tag, compared with the response's)
 };
 
 enum Dst : uint8_t {
@@ -110,11 +122,46 @@ WG_HSC_DEVICE constexpr Step kRespProgram[] = {
     {OP_MAC1KEY, SRC_ZERO, 0, DST_IST}, {OP_MAC1A, SRC_ZERO, 0, DST_NONE}, {OP_MAC1B, SRC_ZERO, 0, DST_NONE},
 };
 
+// k_hs_init_chain. h = H(H(H0 || S_r) || Epub); ck = KDF1(CK0, Epub), from the constant key-block states of CK0;
+// k = KDF2(ck, e S_r) (left in st for the seal of S_pub) and ck = KDF1; h = H(h || encrypted_static); k = KDF2(ck,
+// static-static) (in st for the seal of the timestamp) and ck = KDF1; h = H(h || encrypted_timestamp); mac1 under
+// the peer's key over the 116 bytes.
+WG_HSC_DEVICE constexpr Step kInitProgram[] = {
+    {OP_IH0, SRC_ZERO, 0, DST_H}, {OP_H2, SRC_EPUB, 0, DST_H},
+    {OP_IN32, SRC_EPUB, 0, DST_NONE}, {OP_OUT, SRC_ZERO, 0, DST_X}, WG_HSC_EXPAND1(DST_CK),
+    WG_HSC_EXTRACT(SRC_ES), WG_HSC_EXPAND1(DST_CK), WG_HSC_EXPANDN(SRC_CK, 2, DST_NONE),
+    {OP_IES1, SRC_ZERO, 0, DST_NONE}, {OP_IES2, SRC_ZERO, 0, DST_H},
+    WG_HSC_EXTRACT(SRC_STATIC), WG_HSC_EXPAND1(DST_CK), WG_HSC_EXPANDN(SRC_CK, 2, DST_NONE),
+    {OP_ITS, SRC_ZERO, 0, DST_H},
+    {OP_MAC1KEY, SRC_ZERO, 0, DST_IST}, {OP_MAC1A, SRC_ZERO, 0, DST_NONE}, {OP_IMAC1B, SRC_ZERO, 0, DST_NONE},
+    {OP_IMAC1C, SRC_ZERO, 0, DST_NONE},
+};
+
+// k_hs_fin_chain: kRespProgram without mac1, over the initiator's operands. h = H(h || E_r); ck = KDF1(ck, E_r);
+// ck = KDF1(ck, e E_r); ck = KDF1(ck, S E_r); ck, tau, k = KDF3(ck, psk); h = H(h || tau); the tag of nothing
+// under k, which the kernel compares; send_key, recv_key = KDF2(ck, "") in ck and x.
+WG_HSC_DEVICE constexpr Step kFinProgram[] = {
+    {OP_H2, SRC_ER, 0, DST_H},
+    WG_HSC_EXTRACT(SRC_ER), WG_HSC_EXPAND1(DST_CK),
+    WG_HSC_EXTRACT(SRC_EE), WG_HSC_EXPAND1(DST_CK),
+    WG_HSC_EXTRACT(SRC_ES), WG_HSC_EXPAND1(DST_CK),
+    WG_HSC_EXTRACT(SRC_PSK), WG_HSC_EXPAND1(DST_CK), WG_HSC_EXPANDN(SRC_CK, 2, DST_X),
+    {OP_H2, SRC_X, 0, DST_H},
+    WG_HSC_EXPANDN(SRC_X, 3, DST_X),
+    {OP_PAD, SRC_CK, PAD_OPAD | PAD_SEAL, DST_OST}, {OP_PAD, SRC_CK, PAD_IPAD | PAD_LAST, DST_NONE}, {OP_OUT, SRC_ZERO, 0, DST_X},
+    WG_HSC_EXPAND1(DST_CK),
+    WG_HSC_EXPANDN(SRC_CK, 2, DST_X),
+};
+
 constexpr uint32_t kOpenSteps = sizeof(kOpenProgram) / sizeof(Step);
 constexpr uint32_t kRespSteps = sizeof(kRespProgram) / sizeof(Step);
 static_assert(sizeof(Step) == 4, "a step is one 32-bit word");
 static_assert(kOpenSteps == 28, "k_hs_open: 28 compressions");
 static_assert(kRespSteps == 50, "k_hs_resp_chain: 50 compressions");
+constexpr uint32_t kInitSteps = sizeof(kInitProgram) / sizeof(Step);
+constexpr uint32_t kFinSteps = sizeof(kFinProgram) / sizeof(Step);
+static_assert(kInitSteps == 35, "k_hs_init_chain: 35 compressions");
+static_assert(kFinSteps == 47, "k_hs_fin_chain: 47 compressions");
 
 // the first step of `op` in a program
 template <uint32_t N>

@@ -1,5 +1,5 @@
-// wg_hs_chain.hip — the machine that k_hs_open and k_hs_resp_chain run their Noise chains on (included by
-// wg_capi.hip before wg_hs_open.hip). The chains themselves are data: wg_hs_chain.h.
+// wg_hs_chain.hip — the machine that k_hs_open, k_hs_resp_chain, k_hs_init_chain and k_hs_fin_chain run their
+// Noise chains on (included by wg_capi.hip before wg_hs_open.hip). The chains themselves are data: wg_hs_chain.h.
 //
 // A chain is a row of dependent BLAKE2s compressions per lane, nearly all of them parts of HMAC-BLAKE2s: an
 // HMAC is four compressions (the two key blocks K ^ 0x36.., K ^ 0x5c.. as words, never bytes; the message
@@ -150,6 +150,27 @@ __device__ __forceinline__ void poly_tag(const uint32_t ks[16], const uint32_t a
     if (b < 2) wgd::poly_block_limbs(aad[4 * b], aad[4 * b + 1], aad[4 * b + 2], aad[4 * b + 3], 1u << 24, c);
     else if (b < 2 + CT) wgd::poly_block_limbs(ct[4 * b - 8], ct[4 * b - 7], ct[4 * b - 6], ct[4 * b - 5], 1u << 24, c);
     else wgd::poly_block_limbs(32u, 0u, 16u * CT, 0u, 1u << 24, c);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) h[j] += c[j];
+    wgd::poly_mul<false>(h, r, s5);
+  }
+  wgd::poly_finish(h, ks[4], ks[5], ks[6], ks[7], tag);
+}
+
+// ... for a ciphertext of ct_bytes bytes, 16 (CT - 1) < ct_bytes <= 16 CT: ct holds CT blocks, the last one padded
+// with zeros by the caller (RFC 8439 2.8: pad16), and the length block carries the true byte count. A sibling, so
+// that poly_tag's instantiations stay as they are.
+template <int CT>
+__device__ __forceinline__ void poly_tag_bytes(const uint32_t ks[16], const uint32_t aad[8], const uint32_t* ct, uint32_t ct_bytes,
+                                               uint32_t tag[4]) {
+  uint32_t r[5], s5[5], h[5] = {0u, 0u, 0u, 0u, 0u}, c[5];
+  wgd::poly_r_limbs(ks[0], ks[1], ks[2], ks[3], r);
+  wgd::poly_scale5(r, s5);
+#pragma unroll
+  for (int b = 0; b < 3 + CT; ++b) {
+    if (b < 2) wgd::poly_block_limbs(aad[4 * b], aad[4 * b + 1], aad[4 * b + 2], aad[4 * b + 3], 1u << 24, c);
+    else if (b < 2 + CT) wgd::poly_block_limbs(ct[4 * b - 8], ct[4 * b - 7], ct[4 * b - 6], ct[4 * b - 5], 1u << 24, c);
+    else wgd::poly_block_limbs(32u, 0u, ct_bytes, 0u, 1u << 24, c);
 #pragma unroll
     for (int j = 0; j < 5; ++j) h[j] += c[j];
     wgd::poly_mul<false>(h, r, s5);

@@ -309,6 +309,7 @@ int hs_open_rekey(wg_ctx* c, HsState* t, const uint8_t* static_public) {
   HIPTRY(hipDeviceSynchronize());  // no open queued earlier (on any stream) may still read the old values
   uint8_t* st = (uint8_t*)t->d_stage.p + 256;
   HIPTRY(hipMemcpyAsync(st, host, sizeof host, hipMemcpyHostToDevice, c->stream));
+  HIPTRY(hipMemcpyAsync((uint8_t*)t->d_key.p + 64, host + 64, 32, hipMemcpyHostToDevice, c->stream));  // S_pub, for wg_hs_initiate
   int rc;
   if ((rc = b2s_launch((const wg_b2s_desc*)st, 1, st, 128, (uint8_t*)t->d_key.p + 32, 32, (uint32_t*)(st + 96), c->stream)) != WG_OK)
     return rc;
@@ -352,10 +353,13 @@ int wg_hs_peers_set(wg_ctx* c, const uint8_t* publics, uint32_t n) {
   int rc = WG_OK;
   if (t->d_psec.p && t->d_psec.cap < 32ull * n) HIPTRY(hipMemset(t->d_psec.p, 0, t->d_psec.cap));  // freed below: wiped first
   t->n_peers = 0;
+  if (t->d_ppsk.p) HIPTRY(hipMemset(t->d_ppsk.p, 0, t->d_ppsk.cap));  // every psk is zero again (and the buffer may be freed below)
   if (n) {
     if ((rc = t->d_pslots.ensure(slots.size() * 4)) == WG_OK && (rc = t->d_pin.ensure(32ull + 32ull * n)) == WG_OK &&
-        (rc = t->d_psec.ensure(32ull * n)) == WG_OK && (rc = t->d_pdesc.ensure(36ull * n)) == WG_OK) {
-      hipError_t e = hipMemcpyAsync(t->d_pslots.p, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, c->stream);
+        (rc = t->d_psec.ensure(32ull * n)) == WG_OK && (rc = t->d_pdesc.ensure(36ull * n)) == WG_OK &&
+        (rc = t->d_ppsk.ensure(32ull * n)) == WG_OK) {
+      hipError_t e = hipMemsetAsync(t->d_ppsk.p, 0, t->d_ppsk.cap, c->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(t->d_pslots.p, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, c->stream);
       if (e == hipSuccess) e = hipMemcpyAsync((uint8_t*)t->d_pin.p + 32, publics, 32ull * n, hipMemcpyHostToDevice, c->stream);
       if (e == hipSuccess) e = hipMemcpyAsync(t->d_pdesc.p, desc.data(), 32ull * n, hipMemcpyHostToDevice, c->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -375,7 +379,11 @@ int wg_hs_peers_set(wg_ctx* c, const uint8_t* publics, uint32_t n) {
     H.mask = 15u;
     H.count = 0;
   }
+  HsPskHdr K{};
+  K.psks = (const uint8_t*)(t->n_peers ? t->d_ppsk.p : t->d_pempty.p);
+  K.count = t->n_peers;
   HIPTRY(hipMemcpyAsync(t->d_phdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream));
+  HIPTRY(hipMemcpyAsync(t->d_pskhdr.p, &K, sizeof K, hipMemcpyHostToDevice, c->stream));
   HIPTRY(hipStreamSynchronize(c->stream));
   return rc;
 }

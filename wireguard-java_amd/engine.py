@@ -45,6 +45,11 @@ WG_HS_INIT_DTYPE = np.dtype([("index", "<u4"), ("record", "<u4"), ("sender_index
 WG_HS_SESSION_DTYPE = np.dtype([("index", "<u4"), ("init", "<u4"), ("peer", "<u4"), ("local_index", "<u4"),
                                 ("response", "u1", (92,)), ("remote_index", "<u4"), ("send_key", "u1", (32,)),
                                 ("recv_key", "u1", (32,))])
+WG_HS_PENDING_DTYPE = np.dtype([("state", "<u4"), ("peer", "<u4"), ("local_index", "<u4"), ("_zero", "<u4"),
+                                ("ephemeral", "u1", (32,)), ("hash", "u1", (32,)), ("chain_key", "u1", (32,))])
+WG_HS_ESTABLISHED_DTYPE = np.dtype([("index", "<u4"), ("record", "<u4"), ("pending", "<u4"), ("peer", "<u4"),
+                                    ("local_index", "<u4"), ("remote_index", "<u4"), ("_zero", "<u4", (2,)),
+                                    ("send_key", "u1", (32,)), ("recv_key", "u1", (32,))])
 
 
 def pack_b2s_desc(in_off, out_off, key_off, length, outlen, keylen) -> np.ndarray:
@@ -593,6 +598,110 @@ class Engine:
             d_init.zero_()
             torch.cuda.synchronize(dev)
         return status, sess
+
+    # ---- the initiator's side (wg_hs_psks_set / wg_hs_initiate / wg_hs_finish) -----------------
+    def hs_psks_set(self, psks) -> None:
+        """wg_hs_psks_set: the peers' preshared keys (32 n bytes, or a sequence of 32-byte keys), by position in
+        the table of hs_peers_set, which resets them all to zero; the count must equal the table's."""
+        if not isinstance(psks, (bytes, bytearray, memoryview, np.ndarray)):
+            psks = b"".join(bytes(p) for p in psks)
+        pk = np.frombuffer(bytes(psks), np.uint8).copy()
+        if pk.size % 32:
+            raise L.WgError(L.WG_EINVAL, f"{pk.size} bytes of preshared keys: not a multiple of 32")
+        try:
+            L.check(self._lib.wg_hs_psks_set(self.ctx, pk.ctypes.data if pk.size else None, pk.size // 32))
+        finally:
+            pk[:] = 0
+
+    def hs_initiate(self, peer, ephemerals, timestamps, local_index, status, records, pending, summary,
+                    stream: int | None = None) -> None:
+        """wg_hs_initiate over torch tensors: peer int32 [n] (positions in the peer table), ephemerals uint8
+        [n, 32] or [n * 32] (fresh private keys from the host's CSPRNG; the call zeroes each one it consumed),
+        timestamps uint8 [n, 12] or [n * 12] (TAI64N), local_index int32 [n] (the new sender indices), status
+        int32 [n] (WG_HS_INIT_*), records uint8 [n, 160] (WG_HS_RECORD_DTYPE), pending uint8 [n, 112]
+        (WG_HS_PENDING_DTYPE), summary int32 [4] (n_ok, n_badpeer, n_noeph, 0)."""
+        b = L.WgHsInitiateBatch(peer.data_ptr(), ephemerals.data_ptr(), timestamps.data_ptr(), local_index.data_ptr(),
+                                status.data_ptr(), records.data_ptr(), pending.data_ptr(), summary.data_ptr(),
+                                peer.shape[0], 0)
+        L.check(self._lib.wg_hs_initiate(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def hs_finish(self, records, hs_summary, pending, fin_status, established, fin_summary,
+                  stream: int | None = None) -> None:
+        """wg_hs_finish over torch tensors: records uint8 [n, 160] and hs_summary int32 [4] as hs_check() wrote
+        them on this (the initiator's) context (hs_summary None: all n records), pending uint8 [n_pending, 112] as
+        hs_initiate() wrote it (the call zeroes each entry it consumed), fin_status int32 [n] (WG_HS_FIN_*),
+        established uint8 [n, 96] (WG_HS_ESTABLISHED_DTYPE), fin_summary int32 [4] (n_ok, n_nopending, n_badauth,
+        n_skipped). Check and finish run back to back on one stream."""
+        n_records = hs_summary.data_ptr() + L.WgHsSummary.n_valid.offset if hs_summary is not None else None
+        b = L.WgHsFinishBatch(records.data_ptr(), n_records, pending.data_ptr() if pending.shape[0] else None,
+                              fin_status.data_ptr(), established.data_ptr(), fin_summary.data_ptr(), records.shape[0],
+                              pending.shape[0])
+        L.check(self._lib.wg_hs_finish(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def hs_initiate_host(self, peer: int, ephemeral, timestamp, local_index: int):
+        """One initiation to the peer at this position of the table, with this ephemeral private key (32 bytes),
+        TAI64N timestamp (12 bytes) and sender index: returns (WG_HS_INIT_* status, the 148-byte message, the
+        wg_hs_pending entry as a WG_HS_PENDING_DTYPE scalar; None, None when nothing was initiated). The device
+        copies of the ephemeral and of the pending entry are zeroed before it returns. For the noise mirror and
+        tests."""
+        import torch
+        if len(ephemeral) != 32 or len(timestamp) != 12:
+            raise L.WgError(L.WG_EINVAL, "an ephemeral private key is 32 bytes, a timestamp 12")
+        dev = torch.device("cuda", self.device)
+        d_peer = torch.from_numpy(np.array([peer & 0xFFFFFFFF], np.uint32).view(np.int32)).to(dev)
+        d_eph = torch.from_numpy(np.frombuffer(bytes(ephemeral), np.uint8).copy()).to(dev)
+        d_ts = torch.from_numpy(np.frombuffer(bytes(timestamp), np.uint8).copy()).to(dev)
+        d_li = torch.from_numpy(np.array([local_index & 0xFFFFFFFF], np.uint32).view(np.int32)).to(dev)
+        d_st = torch.zeros(1, dtype=torch.int32, device=dev)
+        d_rec = torch.zeros((1, 160), dtype=torch.uint8, device=dev)
+        d_pend = torch.zeros((1, 112), dtype=torch.uint8, device=dev)
+        d_sum = torch.zeros(4, dtype=torch.int32, device=dev)
+        st = _torch_stream()
+        try:
+            self.hs_initiate(d_peer, d_eph, d_ts, d_li, d_st, d_rec, d_pend, d_sum, stream=st)
+            self.sync(st)
+            status = int(d_st.cpu().numpy()[0])
+            if status != L.WG_HS_INIT_OK:
+                return status, None, None
+            msg = d_rec.cpu().numpy().reshape(-1).view(WG_HS_RECORD_DTYPE)[0]["msg"].tobytes()
+            pend = d_pend.cpu().numpy().reshape(-1).view(WG_HS_PENDING_DTYPE)[0].copy()
+        finally:
+            d_eph.zero_()
+            d_pend.zero_()
+            torch.cuda.synchronize(dev)
+        return status, msg, pend
+
+    def hs_finish_host(self, pending_entry, response):
+        """One 92-byte response against one wg_hs_pending entry (a WG_HS_PENDING_DTYPE scalar) through hs_finish:
+        returns (WG_HS_FIN_* status, the wg_hs_established entry as a WG_HS_ESTABLISHED_DTYPE scalar, or None).
+        The device copies of the pending entry and of the keys are zeroed before it returns. For the noise mirror
+        and tests."""
+        import torch
+        if len(response) != 92:
+            raise L.WgError(L.WG_EINVAL, "a response is 92 bytes")
+        dev = torch.device("cuda", self.device)
+        rec = np.zeros(1, WG_HS_RECORD_DTYPE)
+        rec["len"] = L.WG_HS_RESP_SIZE
+        rec["msg"][0, :92] = np.frombuffer(bytes(response), np.uint8)
+        pe = np.zeros(1, WG_HS_PENDING_DTYPE)
+        pe[0] = pending_entry
+        d_rec = torch.from_numpy(rec.view(np.uint8).reshape(1, 160)).to(dev)
+        d_pend = torch.from_numpy(pe.view(np.uint8).reshape(1, 112)).to(dev)
+        d_st = torch.zeros(1, dtype=torch.int32, device=dev)
+        d_est = torch.zeros((1, 96), dtype=torch.uint8, device=dev)
+        d_sum = torch.zeros(4, dtype=torch.int32, device=dev)
+        st = _torch_stream()
+        try:
+            self.hs_finish(d_rec, None, d_pend, d_st, d_est, d_sum, stream=st)
+            self.sync(st)
+            status = int(d_st.cpu().numpy()[0])
+            est = d_est.cpu().numpy().reshape(-1).view(WG_HS_ESTABLISHED_DTYPE)[0].copy() if int(d_sum.cpu().numpy()[0]) else None
+        finally:
+            d_pend.zero_()
+            d_est.zero_()
+            pe[:] = 0
+            torch.cuda.synchronize(dev)
+        return status, est
 
     def set_receivers(self, receivers) -> None:
         """wg_ctx_set_receivers: device tensor of receiver_index per key slot for

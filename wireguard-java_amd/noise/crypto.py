@@ -35,6 +35,16 @@ class Crypto:
     BLAKE2S_BLOCKBYTES = 64
 
     @staticmethod
+    def TAI64N(millis: int | None = None) -> bytes:
+        """Crypto.TAI64N (Crypto.java:19-27): the long currentTimeMillis() * 1000 + 4611686018427387914 written
+        big-endian into the last 8 of 12 bytes; the first 4 stay zero (the long is positive, so its arithmetic
+        shifts bring in zeros). millis: the clock's value, None for now."""
+        if millis is None:
+            import time
+            millis = time.time_ns() // 1_000_000
+        return bytes(4) + ((millis * 1000 + 4611686018427387914) & 0x7FFFFFFFFFFFFFFF).to_bytes(8, "big")
+
+    @staticmethod
     def HMAC(sum, key, *messages) -> None:
         """Crypto.HMAC (Crypto.java:39-71): sum = HMAC-BLAKE2s(key, messages...) over the 64-byte block, the two
         hashes on the device (wg_blake2s_batch). A key longer than a block is hashed first; the digest is

@@ -1,5 +1,6 @@
-"""ax.xz.wireguard.noise.handshake mirror: SymmetricKeypair, the drop-in boundary, and
-Handshakes.decryptRemoteStatic / ResponderHandshake, the responder's two phases on the device.
+"""ax.xz.wireguard.noise.handshake mirror: SymmetricKeypair, the drop-in boundary,
+Handshakes.decryptRemoteStatic / ResponderHandshake, the responder's two phases on the device, and
+Handshakes.initiateHandshake / InitiatorStageOne, the initiator's two.
 
 Keeps the reference API (SymmetricKeypair.java:20-94): cipher(src, dst) -> counter,
 decipher(counter, src, dst) raising BadPaddingException (AEADBadTagException),
@@ -17,7 +18,7 @@ import numpy as np
 from .. import _lib as L
 from ..engine import Engine, default_engine, desc_as_int64, pack_desc
 from .crypto import AEADBadTagException, Crypto, IllegalStateException, _bytes, _size, _write
-from .keys import NoisePrivateKey, NoisePublicKey
+from .keys import NoisePresharedKey, NoisePrivateKey, NoisePublicKey
 
 
 class Handshakes:
@@ -47,6 +48,81 @@ class Handshakes:
         """Handshakes.responderHandshake (Handshakes.java:47-50): both phases of the responder, on the device."""
         return ResponderHandshake(localKeypair, remoteEphemeral, encryptedStatic, encryptedTimestamp, engine, ephemeral,
                                   localIndex)
+
+    @staticmethod
+    def initiateHandshake(localKeypair: NoisePrivateKey, remotePublicKey: NoisePublicKey,
+                          presharedKey: NoisePresharedKey | None = None, engine: Engine | None = None, ephemeral=None,
+                          timestamp=None, senderIndex: int = 0) -> "InitiatorStageOne":
+        """Handshakes.initiateHandshake (Handshakes.java:43-45): the initiator's first stage, on the device."""
+        return InitiatorStageOne(localKeypair, remotePublicKey, presharedKey, engine, ephemeral, timestamp, senderIndex)
+
+
+class InitiatorStageOne:
+    """Handshakes.InitiatorStageOne (Handshakes.java:52-164): the constructor's chain and the initiation message
+    through wg_hs_initiate, consumeMessageResponse through wg_hs_finish. localKeypair becomes the engine's static
+    key, remotePublicKey its one peer and presharedKey (None: zero) that peer's psk. `ephemeral` is the fresh
+    ephemeral private key (None: 32 bytes of os.urandom, as NoisePrivateKey.newPrivateKey draws them), `timestamp`
+    the 12 bytes that are sealed (None: Crypto.TAI64N() now)."""
+
+    def __init__(self, localKeypair: NoisePrivateKey, remotePublicKey: NoisePublicKey,
+                 presharedKey: NoisePresharedKey | None = None, engine: Engine | None = None, ephemeral=None, timestamp=None,
+                 senderIndex: int = 0):
+        eng = self._engine = engine or default_engine()
+        self._local, self._remote = localKeypair, remotePublicKey
+        self._psk = presharedKey if presharedKey is not None else NoisePresharedKey.zero()
+        self._install()
+        eph = bytes(ephemeral.data() if isinstance(ephemeral, NoisePrivateKey) else ephemeral) if ephemeral is not None \
+            else os.urandom(32)
+        ts = bytes(timestamp) if timestamp is not None else Crypto.TAI64N()
+        status, msg, pending = eng.hs_initiate_host(0, eph, ts, senderIndex)
+        if msg is None:
+            raise L.WgError(L.WG_EINVAL, f"wg_hs_initiate status {status}")
+        self._message, self._pending = msg, pending
+        self._ephemeral_private = eph
+
+    def _install(self):
+        eng = self._engine
+        eng.hs_static_set(self._local.data())
+        eng.hs_peers_set([self._remote.data()])
+        eng.hs_psks_set([self._psk.data()])
+
+    def initiation(self, senderIndex: int | None = None) -> bytes:
+        """The 148-byte message (OutgoingInitiation.java:22-38). Another senderIndex than the constructor's is
+        written into it, with mac1 computed again (InitiationPacket.java:110-120)."""
+        if senderIndex is None or (senderIndex & 0xFFFFFFFF) == int(self._pending["local_index"]):
+            return self._message
+        from .crypto import calculate_mac1
+        head = self._message[:4] + (senderIndex & 0xFFFFFFFF).to_bytes(4, "little") + self._message[8:116]
+        return head + calculate_mac1(head, self._remote.data()) + bytes(16)
+
+    def consumeMessageResponse(self, remoteEphemeral: NoisePublicKey, encryptedEmpty) -> "SymmetricKeypair":
+        """Handshakes.java:119-151: the transport keys, or AEADBadTagException (a BadPaddingException) when
+        encryptedEmpty does not verify; the stage can then be tried on another response, as the reference's can
+        not (its hash and chain key are spent either way)."""
+        empty = _bytes(encryptedEmpty)
+        if len(empty) != 16:
+            raise AEADBadTagException("Tag mismatch")
+        self._install()
+        response = bytes([2, 0, 0, 0]) + bytes(4) + int(self._pending["local_index"]).to_bytes(4, "little") + \
+            remoteEphemeral.data() + empty + bytes(32)
+        status, est = self._engine.hs_finish_host(self._pending, response)
+        if status == L.WG_HS_FIN_BADAUTH:
+            raise AEADBadTagException("Tag mismatch")
+        if est is None:
+            raise L.WgError(L.WG_EINVAL, f"wg_hs_finish status {status}")
+        kp = SymmetricKeypair(est["send_key"].tobytes(), est["recv_key"].tobytes(), engine=self._engine)
+        est["send_key"] = 0
+        est["recv_key"] = 0
+        return kp
+
+    def getLocalEphemeral(self) -> NoisePrivateKey:
+        return NoisePrivateKey(self._ephemeral_private, NoisePublicKey(self._message[8:40]))
+
+    def getEncryptedStatic(self) -> bytes:
+        return self._message[40:88]
+
+    def getEncryptedTimestamp(self) -> bytes:
+        return self._message[88:116]
 
 
 class ResponderHandshake:

@@ -82,6 +82,36 @@ class NoisePublicKey:
         return hash(self._data)
 
 
+class NoisePresharedKey:
+    """NoisePresharedKey.java: 32 bytes."""
+    LENGTH = 32
+
+    def __init__(self, data):
+        if data is None:
+            raise TypeError("data")
+        data = bytes(data)
+        if len(data) != self.LENGTH:
+            raise ValueError("NoisePublicKey must be 32 bytes")  # (the reference's message)
+        self._data = data
+
+    def data(self) -> bytes:
+        return self._data
+
+    @staticmethod
+    def fromBase64(text: str) -> "NoisePresharedKey":
+        return NoisePresharedKey(base64.b64decode(text))
+
+    @staticmethod
+    def zero() -> "NoisePresharedKey":
+        return NoisePresharedKey(bytes(NoisePresharedKey.LENGTH))
+
+    def __eq__(self, other):
+        return isinstance(other, NoisePresharedKey) and self._data == other._data
+
+    def __hash__(self):
+        return hash(self._data)
+
+
 class NoisePrivateKey:
     """NoisePrivateKey.java:12-56: the public key is derived when the key is made; sharedSecret ignores
     calculateAgreement's result, so a low-order public key yields 32 zero bytes."""
