@@ -453,8 +453,9 @@ int wg_tx_plan(wg_ctx* ctx, const wg_tx_batch* batch, void* stream);
  *   open-addressing hash table built on the host: capacity = the smallest power of two >= max(16, 4 n),
  *   8-byte entries {index, key_slot + 1} (0: empty), bucket = fmix32(index) & (capacity - 1) with
  *   MurmurHash3's 32-bit finaliser, linear probing. Its header (entries, mask, count) keeps one device address for
- *   the life of the context, so a captured plan needs no re-capture after a table change. There is no
- *   single-entry insert or remove: rekeying one peer sends the table again.
+ *   the life of the context, so a captured plan needs no re-capture after a table change. Without
+ *   wg_rx_sessions_reserve there is no single-entry insert or remove, and rekeying one peer sends the table
+ *   again; with it the device inserts and retires entries ("handshake sessions installed on the device" below).
  *
  * wg_rx_plan(ctx, b, stream): wire packet i is wire[o .. o + wl), o = pkt_off[i], wl = pkt_len[i]. The
  *   checks, in this order:
@@ -837,8 +838,8 @@ int wg_hs_open(wg_ctx* ctx, const wg_hs_open_batch* batch, void* stream);
  *   between workgroups, nothing about a call on the host: a captured plan + check + dh + open + respond
  *   replays; between replays the host refreshes ephemerals and local_index in place. The three ladders of an
  *   entry run in three neighbouring lanes. No branch, address or loop bound depends on an ephemeral's value, a
- *   DH result, ck, tau, k or a transport key, except the all-zero test of the raw ephemeral. The host installs
- *   send_key / recv_key with wg_keys_set and local_index with wg_rx_sessions_set. */
+ *   DH result, ck, tau, k or a transport key, except the all-zero test of the raw ephemeral. wg_hs_install
+ *   ("handshake sessions installed on the device" below) turns the sessions into transport sessions. */
 #define WG_HS_RESP_OK 0u
 #define WG_HS_RESP_NOPEER 1u       /* SKIP_NEWPEER, and the entry's peer is WG_HS_NOPEER */
 #define WG_HS_RESP_NOEPH 2u        /* the entry's ephemeral is all zero */
@@ -936,8 +937,8 @@ int wg_hs_respond(wg_ctx* ctx, const wg_hs_respond_batch* batch, void* stream);
  *   call on the host: a captured check + finish replays.
  *   For both calls: no branch, address or loop bound depends on an ephemeral's value, a DH result, ck, tau, k, a
  *   psk's value or a transport key, except the all-zero test of the raw ephemeral; the receiver index and the
- *   peer position are public. The host installs send_key / recv_key with wg_keys_set and local_index with
- *   wg_rx_sessions_set. */
+ *   peer position are public. wg_hs_install ("handshake sessions installed on the device" below) turns the
+ *   established entries into transport sessions. */
 #define WG_HS_INIT_OK 0u
 #define WG_HS_INIT_BADPEER 1u /* peer[k] is not a position in the peer table */
 #define WG_HS_INIT_NOEPH 2u   /* the entry's ephemeral is all zero */
@@ -995,6 +996,108 @@ typedef struct wg_hs_finish_batch {
 int wg_hs_psks_set(wg_ctx* ctx, const uint8_t* psks_host /* 32 n bytes */, uint32_t n);
 int wg_hs_initiate(wg_ctx* ctx, const wg_hs_initiate_batch* batch, void* stream);
 int wg_hs_finish(wg_ctx* ctx, const wg_hs_finish_batch* batch, void* stream);
+
+/* ---- handshake sessions installed on the device ----
+ * What the reference does with a finished handshake (SessionManager.setSession: a new EstablishedSession around a
+ * new SymmetricKeypair(send, recv), reachable under its local index through PeerList) for a ring of wg_hs_session
+ * or wg_hs_established entries, without a key leaving the device: the next wg_tx_plan / wg_seal_batch(WG_F_FRAME)
+ * and wg_rx_plan / wg_open_batch / wg_rx_check on the same stream already use the new sessions.
+ *
+ * wg_rx_sessions_reserve(ctx, max_sessions): gives the receiver-index table a fixed capacity C, the smallest power
+ *   of two >= max(16, 4 max_sessions), of the context's own entries (a table that is empty too), and allocates the
+ *   install's scratch (one word per key slot, four control words). Synchronous, like wg_rx_sessions_set; the
+ *   table's current live entries are rebuilt into the new capacity and its retired entries are dropped.
+ *   Afterwards wg_rx_sessions_set builds into max(C, the capacity of its own rule). A context that never
+ *   reserves builds exactly the tables described above. max_sessions above 2^29: WG_E2BIG.
+ *   The table's header gains `used`, the number of live + retired entries. A retired entry is {index,
+ *   0xFFFFFFFF} in the same 8-byte format: a lookup walks over it (it is not empty) and never matches it. No
+ *   key slot is 0xFFFFFFFE, so no table built by wg_rx_sessions_set holds one.
+ * wg_rx_sessions_retire(ctx, indices_dev, n, n_retired_dev, stream): asynchronous on `stream`. Every index of
+ *   the device array that is live in the table becomes a retired entry, by a 64-bit compare-and-swap on the
+ *   entry, so equal indices in one call retire it once. *n_retired_dev (device, 4-byte aligned, may be NULL) =
+ *   the number of entries the call retired. There is no per-position status: nothing depends on thread order.
+ *   A retired index plans as WG_PKT_NOSESSION; the entries behind it in its probe sequence are still found.
+ *   `used` does not fall: only a rebuild (wg_rx_sessions_set, wg_rx_sessions_reserve) reclaims retired entries.
+ *   The keys are not touched: wg_keys_zero stays the host's call.
+ * wg_rx_sessions_count(ctx, &live, &retired): synchronous, after everything queued on the device (either
+ *   pointer may be NULL).
+ *
+ * wg_hs_install(ctx, b, stream): entries = wg_hs_respond's sessions (source WG_HS_INSTALL_SESSIONS, 176 B) or
+ *   wg_hs_finish's established (WG_HS_INSTALL_ESTABLISHED, 96 B); n_entries a device pointer to their number
+ *   (&wg_hs_respond_summary.n_ok / &wg_hs_finish_summary.n_ok; NULL: all n), read on the device. The position p of
+ *   entry j is sessions[j].init or established[j].pending: the index under which the host chose local_index for
+ *   that handshake. Under the same index it chooses, before it launches the chain, the entry's two key slots
+ *   send_slot[p] and recv_slot[p] (n_slots entries each), so nothing is read back to pick slots. For every j <
+ *   min(*n_entries, n), in this order, each step's test being against all entries that passed the steps before
+ *   it, whether or not they pass later ones, and the lower j winning:
+ *   1. WG_HS_INST_BADSLOT: p >= n_slots; or one of the two slots is outside [slot_first, slot_first + slot_count),
+ *      the slot range this call may write, or >= the key table; or send_slot[p] == recv_slot[p].
+ *   2. WG_HS_INST_DUPSLOT: a lower j that passed step 1 names one of this entry's slots, as send or as recv.
+ *      (Two authentic responses to one pending entry, which wg_hs_finish emits both: the first is installed.)
+ *   3. WG_HS_INST_DUPINDEX: local_index is live in the table at the call's start, or it is the local_index of a
+ *      lower j that passed steps 1-2. A retired entry of that index does not count.
+ *   4. WG_HS_INST_FULL, all or nothing: if used + (the entries that passed 1-3) > C / 2, every one of them is FULL
+ *      and the table is unchanged. The table is thus never more than half full, which bounds every probe walk.
+ *   5. WG_HS_INST_OK. keys[send_slot] = send_key, keys[recv_slot] = recv_key; the send counters of both slots
+ *      become 0 and their replay windows empty (top, every window word), as after wg_keys_set; {local_index ->
+ *      recv_slot} is inserted and `used` grows by one; receivers[send_slot] = remote_index when receivers (the
+ *      table given to wg_ctx_set_receivers, >= key_slots entries) is not NULL; with WG_HS_INSTALL_WIPE the
+ *      entry's 64 key bytes are zeroed. A refused entry keeps its keys: the host can fall back to wg_keys_set.
+ *   inst_status[j] is written for the covered j and nothing behind them; nothing else of a refused entry is
+ *   written. summary = {n_ok, n_badslot, n_dup (DUPSLOT + DUPINDEX), n_full}.
+ *   n = 0 is a no-op. Without wg_rx_sessions_reserve: WG_EINVAL. Unknown flags or source, entries not 16-byte
+ *   aligned (summary: 8; the others: 4), or an output (entries, inst_status, summary, receivers) that overlaps
+ *   another output or an input: WG_EINVAL. n above 2^30: WG_E2BIG.
+ *   Which of several equal slots or indices wins depends on no thread order: a launch over the claim words, one
+ *   in which every entry leaves its position in its slots' words (atomicMin), one that places transient table
+ *   entries {index, 0x80000000 | j} (compare-and-swap to claim a bucket, atomicMin on the position), one that
+ *   counts the entries that passed steps 1-3, and the commit, with one workgroup per entry (the window clear is
+ *   up to 8 KiB per slot). Kernel boundaries order them; no workgroup waits for another. Every scratch word is
+ *   written before it is read in each call and nothing about a call lives on the host, so a captured ... ->
+ *   wg_hs_respond -> wg_hs_install replays; the host refreshes ephemerals, local_index and the two slot arrays in
+ *   place between replays. The scratch holds positions only, never key bytes. A ring with more new indices than
+ *   the table has empty buckets is handled (all FULL), but slowly: reserve for the sessions you mean to hold.
+ *   Constant time: keys move by straight copies (load, store, zero); no branch, address or loop bound depends on
+ *   a key byte. Slots, indices and positions are public.
+ *   The host's copy of a key. wg_seal1 / wg_open1 and the queues (wg_submit_*) seal with the host's mirror of the
+ *   key table, which a device install cannot update. The call therefore marks the mirror of every slot of
+ *   [slot_first, slot_first + slot_count) as holding no key, when it is made (or captured): those paths then
+ *   return WG_ENOKEY on such a slot instead of sealing under a stale key, until a later wg_keys_set on the slot,
+ *   which works as before. Device-installed slots are batch-path only.
+ *   Ordering. The call waits for, and is waited for by, the receive plans, the replay checks (if a window is
+ *   enabled) and the transmit plans (if the transmit state exists) of every stream. Send counters or windows that
+ *   do not exist when the call is made or captured are not reset (they start at zero when they are created); a
+ *   captured install holds the windows' addresses, so enabling a larger window afterwards needs a new capture. The
+ *   key table itself has no ordering with seals and opens on other streams, today or with this call: install on
+ *   the stream that seals and opens next, or synchronise. */
+#define WG_HS_INST_OK 0u
+#define WG_HS_INST_BADSLOT 1u  /* position or slot out of range, or send slot == recv slot */
+#define WG_HS_INST_DUPSLOT 2u  /* a lower entry names one of the slots */
+#define WG_HS_INST_DUPINDEX 3u /* local_index is live in the table, or a lower entry's */
+#define WG_HS_INST_FULL 4u     /* the call's new entries would fill the table past C / 2: none is installed */
+#define WG_HS_INSTALL_SESSIONS 0u    /* source: wg_hs_session[] */
+#define WG_HS_INSTALL_ESTABLISHED 1u /* source: wg_hs_established[] */
+#define WG_HS_INSTALL_WIPE 1u        /* flags: zero an installed entry's send_key and recv_key */
+typedef struct wg_hs_install_summary {
+  uint32_t n_ok, n_badslot, n_dup, n_full;
+} wg_hs_install_summary;
+typedef struct wg_hs_install_batch {
+  void* entries;             /* device, 16-byte aligned: wg_hs_session[] or wg_hs_established[]; in and out with WIPE */
+  const uint32_t* n_entries; /* device: &wg_hs_respond_summary.n_ok / &wg_hs_finish_summary.n_ok; NULL: all n */
+  const uint32_t* send_slot; /* device, n_slots entries, by position */
+  const uint32_t* recv_slot; /* device, n_slots entries */
+  uint32_t* receivers;       /* device, >= key_slots entries (the table of wg_ctx_set_receivers), or NULL */
+  uint32_t* inst_status;     /* device, n entries, WG_HS_INST_* */
+  wg_hs_install_summary* summary; /* device, 16 bytes, 8-byte aligned */
+  uint32_t n, n_slots;
+  uint32_t slot_first, slot_count; /* the device-owned slot range of this call */
+  uint32_t source;           /* WG_HS_INSTALL_SESSIONS or WG_HS_INSTALL_ESTABLISHED */
+  uint32_t flags;            /* WG_HS_INSTALL_WIPE */
+} wg_hs_install_batch;
+int wg_rx_sessions_reserve(wg_ctx* ctx, uint32_t max_sessions);
+int wg_rx_sessions_retire(wg_ctx* ctx, const uint32_t* indices_dev, uint32_t n, uint32_t* n_retired_dev, void* stream);
+int wg_rx_sessions_count(wg_ctx* ctx, uint32_t* live, uint32_t* retired);
+int wg_hs_install(wg_ctx* ctx, const wg_hs_install_batch* batch, void* stream);
 
 int wg_seal1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* pt, uint32_t len, uint8_t* out);
 int wg_open1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* in, uint32_t len, uint8_t* pt);

@@ -74,6 +74,14 @@ WG_HS_FIN_NOPENDING = 1
 WG_HS_FIN_BADAUTH = 2
 WG_HS_FIN_SKIPPED = 3
 WG_HS_FIN_BADDESC = 4
+WG_HS_INST_OK = 0
+WG_HS_INST_BADSLOT = 1
+WG_HS_INST_DUPSLOT = 2
+WG_HS_INST_DUPINDEX = 3
+WG_HS_INST_FULL = 4
+WG_HS_INSTALL_SESSIONS = 0
+WG_HS_INSTALL_ESTABLISHED = 1
+WG_HS_INSTALL_WIPE = 1
 WG_MAX_FILTERS = 65536
 WG_NO_FILTER = 0xFFFFFFFF
 WG_LEN_INVALID = 0xFFFFFFFF
@@ -272,6 +280,21 @@ class WgHsFinishBatch(ctypes.Structure):
                 ("n", ctypes.c_uint32), ("n_pending", ctypes.c_uint32)]
 
 
+class WgHsInstallSummary(ctypes.Structure):
+    """wg_hs_install_summary: totals of one wg_hs_install call."""
+    _fields_ = [("n_ok", ctypes.c_uint32), ("n_badslot", ctypes.c_uint32), ("n_dup", ctypes.c_uint32),
+                ("n_full", ctypes.c_uint32)]
+
+
+class WgHsInstallBatch(ctypes.Structure):
+    """wg_hs_install_batch: one wg_hs_install call (device pointers)."""
+    _fields_ = [("entries", ctypes.c_void_p), ("n_entries", ctypes.c_void_p), ("send_slot", ctypes.c_void_p),
+                ("recv_slot", ctypes.c_void_p), ("receivers", ctypes.c_void_p), ("inst_status", ctypes.c_void_p),
+                ("summary", ctypes.c_void_p), ("n", ctypes.c_uint32), ("n_slots", ctypes.c_uint32),
+                ("slot_first", ctypes.c_uint32), ("slot_count", ctypes.c_uint32), ("source", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32)]
+
+
 class WgCompletion(ctypes.Structure):
     """wg_completion: one reaped packet of a wg_queue."""
     _fields_ = [("user", ctypes.c_uint64), ("counter", ctypes.c_uint64), ("data", ctypes.c_void_p),
@@ -294,6 +317,7 @@ assert ctypes.sizeof(WgHsBatch) == 80
 assert ctypes.sizeof(WgX25519Desc) == 32 and ctypes.sizeof(WgHsDhBatch) == 40
 assert ctypes.sizeof(WgHsInit) == 144 and ctypes.sizeof(WgHsOpenSummary) == 16 and ctypes.sizeof(WgHsOpenBatch) == 64
 assert ctypes.sizeof(WgHsSession) == 176 and ctypes.sizeof(WgHsRespondSummary) == 16 and ctypes.sizeof(WgHsRespondBatch) == 64
+assert ctypes.sizeof(WgHsInstallSummary) == 16 and ctypes.sizeof(WgHsInstallBatch) == 80
 assert ctypes.sizeof(WgPkt) == 32 and ctypes.sizeof(WgAeadDesc) == 64 and ctypes.sizeof(WgPrefix) == 18
 
 # (name, restype, argtypes) for every symbol include/wgaead.h declares
@@ -348,6 +372,10 @@ SIGNATURES = [
     ("wg_hs_psks_set", _I, [_VP, _VP, _U32]),
     ("wg_hs_initiate", _I, [_VP, ctypes.POINTER(WgHsInitiateBatch), _VP]),
     ("wg_hs_finish", _I, [_VP, ctypes.POINTER(WgHsFinishBatch), _VP]),
+    ("wg_rx_sessions_reserve", _I, [_VP, _U32]),
+    ("wg_rx_sessions_retire", _I, [_VP, _VP, _U32, _VP, _VP]),
+    ("wg_rx_sessions_count", _I, [_VP, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    ("wg_hs_install", _I, [_VP, ctypes.POINTER(WgHsInstallBatch), _VP]),
     ("wg_seal1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_open1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_pp_config", _I, [_VP, _U32, _U32]),

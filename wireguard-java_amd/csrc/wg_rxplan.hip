@@ -19,6 +19,13 @@
 // wave walks as long as the longest of its 64) and ends at an empty entry. Its header sits at a fixed
 // device address and names the entries (wg_plan.hip, fixed headers).
 //
+// A table the device can change. wg_rx_sessions_reserve gives the table a fixed capacity C of the context's
+// own entries; wg_hs_install (wg_hs_install.hip) then inserts into it and wg_rx_sessions_retire turns a live
+// entry into a retired one, {index, 0xFFFFFFFF}: not empty (a probe walk goes on behind it), not a match.
+// `used` counts live + retired entries and never exceeds C / 2, which bounds every walk; only a rebuild on the
+// host (wg_rx_sessions_set, wg_rx_sessions_reserve) drops the retired ones. A context that never reserves
+// builds exactly the tables it built before there was a reserve.
+//
 // Ranks. The plan needs two stable ranks over the batch (the handshake list, the 64-bit prefix of the
 // packed plaintext offsets) and the deliver one (the item list). Both are a rank_launch of wg_plan.hip,
 // with no wait between workgroups (no spin on another block's flag, no assumption about dispatch order):
@@ -40,10 +47,19 @@
 
 namespace {
 
+constexpr uint32_t kRxRetired = 0xFFFFFFFFu;    // high word of a retired entry (no key slot is 0xFFFFFFFE)
+constexpr uint32_t kRxTransient = 0x80000000u;  // high word 0x80000000 | j: entry j of a running wg_hs_install
+
 struct RxSessHdr {  // at a fixed device address; a table change rewrites it (and may move the entries)
-  const uint2* entries;  // capacity x {index, key slot + 1 (0: empty)}
+  const uint2* entries;  // capacity x {index, key slot + 1 (0: empty, kRxRetired: retired)}
   uint32_t mask;         // capacity - 1; bucket = mix32(index) & mask
-  uint32_t count;
+  uint32_t count;        // live entries
+  uint32_t used;         // live + retired entries
+  uint32_t _pad;
+};
+
+struct RxInstCtl {  // wg_hs_install's words between its launches (written by its first launch in every call)
+  uint32_t used0, n_cand, n_badslot, n_dup;
 };
 
 struct RxPlanState {
@@ -52,18 +68,30 @@ struct RxPlanState {
   DevBuf d_ent;    // the entries of the current table
   DevBuf d_code;   // per packet: {status, key slot, counter lo, counter hi}
   DevBuf d_part;   // per workgroup: {bytes lo, bytes hi, count, count}, then their exclusive prefixes
+  uint32_t reserved = 0;  // wg_rx_sessions_reserve's capacity C (0: never reserved)
+  DevBuf d_claim;  // wg_hs_install: per key slot, the lowest entry that names it
+  DevBuf d_ctl;    // wg_hs_install: RxInstCtl
   StreamOrder order;  // last plan / deliver / table write
 };
 
 const PlanWords kRxPlanWords{"receive plan", "packets", "wg_rx_reserve"};
 const PlanWords kRxDeliverWords{"receive deliver", "packets", "wg_rx_reserve"};
+const PlanWords kRxRetireWords{"session retire", "indices", "wg_rx_sessions_reserve"};
 
-void rxp_header(const RxPlanState* t, uint32_t n, bool own, RxSessHdr* H) {
+uint32_t rxp_capacity(uint32_t n) {  // the smallest power of two >= max(16, 4 n)
   uint32_t cap = 16;
-  while (own && (uint64_t)cap < 4ull * n) cap <<= 1;
+  while ((uint64_t)cap < 4ull * n) cap <<= 1;
+  return cap;
+}
+
+// a reserved table keeps the context's own entries even when it is empty: the device inserts into them
+void rxp_header(const RxPlanState* t, uint32_t n, bool own, RxSessHdr* H) {
+  const uint32_t cap = own ? std::max(rxp_capacity(n), t->reserved) : 16u;
   H->entries = (const uint2*)(own ? t->d_ent.p : t->d_empty.p);
   H->mask = cap - 1u;
   H->count = own ? n : 0u;
+  H->used = H->count;
+  H->_pad = 0u;
 }
 
 // The receive-plan state, allocated at the first wg_rx_sessions_set / wg_rx_reserve / wg_rx_plan /
@@ -103,6 +131,41 @@ int rxp_begin(RxPlanState* t, hipStream_t s, bool capturing, uint32_t n, const P
   return plan_begin(t->order, s, capturing, rxp_scratch_fits(t, n), [&] { return rxp_scratch_grow(t, n); }, w, n);
 }
 
+// Replaces the whole table by n live entries (host pointers), built on the host; nothing changes on a bad
+// argument. Synchronous. Caller holds c->mu and the device.
+int rxp_table_set(wg_ctx* c, RxPlanState* t, const uint32_t* indices, const uint32_t* slots, uint32_t n) {
+  const bool own = n != 0 || t->reserved != 0;
+  RxSessHdr H;
+  rxp_header(t, n, own, &H);
+  std::vector<uint2> ent(own ? (size_t)H.mask + 1 : 0, make_uint2(0u, 0u));
+  for (uint32_t k = 0; k < n; ++k) {
+    if (slots[k] >= c->key_slots) return fail(WG_ERANGE, "session %u: key slot %u >= %u", k, slots[k], c->key_slots);
+    uint32_t b = mix32(indices[k]) & H.mask;
+    while (ent[b].y) {
+      if (ent[b].x == indices[k]) return fail(WG_EINVAL, "session %u: receiver index 0x%08x repeats", k, indices[k]);
+      b = (b + 1u) & H.mask;
+    }
+    ent[b] = make_uint2(indices[k], slots[k] + 1u);
+  }
+  int rc;
+  HIPTRY(hipDeviceSynchronize());  // the entries may move: no plan launched earlier (on any stream) may still read them
+  if (own) {
+    if ((rc = t->d_ent.ensure(ent.size() * sizeof(uint2))) != WG_OK) {
+      t->reserved = 0;
+      rxp_header(t, 0, false, &H);  // the old entries are gone: no sessions, no reserve
+      (void)hipMemcpyAsync(t->d_hdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream);
+      (void)hipStreamSynchronize(c->stream);
+      return rc;
+    }
+    H.entries = (const uint2*)t->d_ent.p;
+    HIPTRY(hipMemcpyAsync(t->d_ent.p, ent.data(), ent.size() * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPTRY(hipMemcpyAsync(t->d_hdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream));
+  if ((rc = t->order.mark(c->stream)) != WG_OK) return rc;
+  HIPTRY(hipStreamSynchronize(c->stream));
+  return WG_OK;
+}
+
 }  // namespace
 
 // ---- device -------------------------------------------------------------------------------
@@ -139,19 +202,51 @@ struct RxDeliverParams {
 };
 
 // key slot + 1 of a receiver index, 0 if the table does not hold it. Two entries of the probe sequence
-// are fetched per round trip (each one 8-B load): a wave walks as long as its longest chain.
+// are fetched per round trip (each one 8-B load): a wave walks as long as its longest chain. A retired
+// entry is walked over: it is not empty, and it does not match (its index may be live again behind it).
 __device__ __forceinline__ uint32_t rx_session(const RxSessHdr& H, uint32_t index) {
   const uint64_t* ent = (const uint64_t*)H.entries;  // {index, key slot + 1} = low, high word
   uint32_t b = mix32(index);
-  for (uint32_t probes = 0; probes <= H.mask; probes += 2u) {  // (a table a quarter full ends the walk long before)
+  for (uint32_t probes = 0; probes <= H.mask; probes += 2u) {  // (a table at most half full ends the walk long before)
     const uint64_t e0 = ent[b & H.mask], e1 = ent[(b + 1u) & H.mask];
-    if (!(uint32_t)(e0 >> 32)) return 0u;
-    if ((uint32_t)e0 == index) return (uint32_t)(e0 >> 32);
-    if (!(uint32_t)(e1 >> 32)) return 0u;
-    if ((uint32_t)e1 == index) return (uint32_t)(e1 >> 32);
+    const uint32_t h0 = (uint32_t)(e0 >> 32), h1 = (uint32_t)(e1 >> 32);
+    if (!h0) return 0u;
+    if ((uint32_t)e0 == index && h0 != kRxRetired) return h0;
+    if (!h1) return 0u;
+    if ((uint32_t)e1 == index && h1 != kRxRetired) return h1;
     b += 2u;
   }
   return 0u;
+}
+
+// One index per thread: a live entry becomes a retired one by a 64-bit CAS, so of equal indices in one call
+// exactly one thread retires it (and counts it).
+__global__ void __launch_bounds__(256) k_rx_retire(RxSessHdr* hdr, const uint32_t* indices, uint32_t n, uint32_t* n_retired) {
+  __shared__ uint32_t s_cnt[4];
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const RxSessHdr H = *hdr;
+  bool mine = false;
+  if (i < n) {
+    const uint32_t index = indices[i];
+    unsigned long long* ent = (unsigned long long*)H.entries;
+    uint32_t b = mix32(index);
+    for (uint32_t probes = 0; probes <= H.mask; ++probes, ++b) {
+      unsigned long long* e = ent + (b & H.mask);
+      const unsigned long long v = *e;
+      const uint32_t h = (uint32_t)(v >> 32);
+      if (!h) break;
+      if ((uint32_t)v == index && h != kRxRetired) {  // the one live entry of this index
+        mine = atomicCAS(e, v, (unsigned long long)index | ((unsigned long long)kRxRetired << 32)) == v;
+        break;
+      }
+    }
+  }
+  uint32_t r, total;
+  block_rank(mine, s_cnt, r, total);
+  if (threadIdx.x == 0 && total) {
+    atomicSub(&hdr->count, total);
+    if (n_retired) atomicAdd(n_retired, total);
+  }
 }
 
 // Steps 1-5 of wg_rx_plan and, in AFTER mode, step 6; writes the packet's code and the range's sums.
@@ -290,32 +385,66 @@ int wg_rx_sessions_set(wg_ctx* c, const uint32_t* indices, const uint32_t* slots
   RxPlanState* t;
   int rc;
   if ((rc = rxp_get(c, &t)) != WG_OK) return rc;
+  return rxp_table_set(c, t, indices, slots, n);
+}
+
+int wg_rx_sessions_reserve(wg_ctx* c, uint32_t max_sessions) {
+  if (!c) return fail(WG_EINVAL, "NULL context");
+  if (max_sessions > 0x20000000u) return fail(WG_E2BIG, "session table of %u entries", max_sessions);
+  if (c->key_slots >= kRxTransient) return fail(WG_EINVAL, "key table too large for a device-owned session table");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  RxPlanState* t;
+  int rc;
+  if ((rc = rxp_get(c, &t)) != WG_OK) return rc;
+  if ((rc = t->d_claim.ensure((size_t)c->key_slots * 4)) != WG_OK || (rc = t->d_ctl.ensure(sizeof(RxInstCtl))) != WG_OK) return rc;
+  // the live entries of the current table, in table order (retired ones are dropped by the rebuild)
+  HIPTRY(hipDeviceSynchronize());
   RxSessHdr H;
-  rxp_header(t, n, n != 0, &H);
-  std::vector<uint2> ent(n ? (size_t)H.mask + 1 : 0, make_uint2(0u, 0u));
-  for (uint32_t k = 0; k < n; ++k) {
-    if (slots[k] >= c->key_slots) return fail(WG_ERANGE, "session %u: key slot %u >= %u", k, slots[k], c->key_slots);
-    uint32_t b = mix32(indices[k]) & H.mask;
-    while (ent[b].y) {
-      if (ent[b].x == indices[k]) return fail(WG_EINVAL, "session %u: receiver index 0x%08x repeats", k, indices[k]);
-      b = (b + 1u) & H.mask;
+  HIPTRY(hipMemcpy(&H, t->d_hdr.p, sizeof H, hipMemcpyDeviceToHost));
+  std::vector<uint2> old(H.used ? (size_t)H.mask + 1 : 0);
+  if (!old.empty()) HIPTRY(hipMemcpy(old.data(), H.entries, old.size() * sizeof(uint2), hipMemcpyDeviceToHost));
+  std::vector<uint32_t> indices, slots;
+  for (const uint2& e : old)
+    if (e.y && e.y != kRxRetired) {
+      indices.push_back(e.x);
+      slots.push_back(e.y - 1u);
     }
-    ent[b] = make_uint2(indices[k], slots[k] + 1u);
+  const uint32_t before = t->reserved;
+  t->reserved = rxp_capacity(max_sessions);
+  if ((rc = rxp_table_set(c, t, indices.data(), slots.data(), (uint32_t)indices.size())) != WG_OK && t->reserved) t->reserved = before;
+  return rc;
+}
+
+int wg_rx_sessions_retire(wg_ctx* c, const uint32_t* indices_dev, uint32_t n, uint32_t* n_retired_dev, void* stream) {
+  if (!c || (!indices_dev && n)) return fail(WG_EINVAL, "NULL argument");
+  if ((((uintptr_t)indices_dev) | ((uintptr_t)n_retired_dev)) & 3u) return fail(WG_EINVAL, "indices / n_retired must be 4-byte aligned");
+  hipStream_t s = pick_stream(c, stream);
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  const bool capturing = stream_capturing(s);
+  if (capturing && !c->rxp)
+    return fail(WG_EINVAL, "session retire on a capturing stream before any wg_rx_* planning call: call wg_rx_sessions_reserve first");
+  RxPlanState* t;
+  int rc;
+  if ((rc = rxp_get(c, &t)) != WG_OK) return rc;
+  if (!capturing && (rc = t->order.after_last(s)) != WG_OK) return rc;
+  if (n_retired_dev) HIPTRY(hipMemsetAsync(n_retired_dev, 0, 4, s));
+  if (n) hipLaunchKernelGGL(wgrp::k_rx_retire, dim3(rank_blocks(n)), dim3(256), 0, s, (RxSessHdr*)t->d_hdr.p, indices_dev, n, n_retired_dev);
+  return plan_end(t->order, s, capturing, kRxRetireWords);
+}
+
+int wg_rx_sessions_count(wg_ctx* c, uint32_t* live, uint32_t* retired) {
+  if (!c) return fail(WG_EINVAL, "NULL context");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  RxSessHdr H{};
+  if (c->rxp) {
+    HIPTRY(hipDeviceSynchronize());  // after everything queued, on any stream
+    HIPTRY(hipMemcpy(&H, c->rxp->d_hdr.p, sizeof H, hipMemcpyDeviceToHost));
   }
-  HIPTRY(hipDeviceSynchronize());  // the entries may move: no plan launched earlier (on any stream) may still read them
-  if (n) {
-    if ((rc = t->d_ent.ensure(ent.size() * sizeof(uint2))) != WG_OK) {
-      rxp_header(t, 0, false, &H);  // the old entries are gone: no sessions
-      (void)hipMemcpyAsync(t->d_hdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream);
-      (void)hipStreamSynchronize(c->stream);
-      return rc;
-    }
-    H.entries = (const uint2*)t->d_ent.p;
-    HIPTRY(hipMemcpyAsync(t->d_ent.p, ent.data(), ent.size() * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
-  }
-  HIPTRY(hipMemcpyAsync(t->d_hdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream));
-  if ((rc = t->order.mark(c->stream)) != WG_OK) return rc;
-  HIPTRY(hipStreamSynchronize(c->stream));
+  if (live) *live = H.count;
+  if (retired) *retired = H.used - H.count;
   return WG_OK;
 }
 

@@ -327,6 +327,43 @@ class Engine:
         one is captured into a graph: a capturing stream cannot allocate)."""
         L.check(self._lib.wg_rx_reserve(self.ctx, max_packets))
 
+    def rx_sessions_reserve(self, max_sessions: int) -> None:
+        """wg_rx_sessions_reserve: a session table of fixed capacity (the smallest power of two >= max(16,
+        4 max_sessions)) that hs_install() inserts into and rx_sessions_retire() retires from, and the install's
+        scratch; the current live entries are kept. Needed before hs_install()."""
+        L.check(self._lib.wg_rx_sessions_reserve(self.ctx, max_sessions))
+
+    def rx_sessions_retire(self, indices, n_retired=None, stream: int | None = None) -> None:
+        """wg_rx_sessions_retire over torch tensors: indices int32 [n] (receiver indices; the live ones become
+        retired entries), n_retired int32 [1] or None (how many the call retired). Asynchronous."""
+        L.check(self._lib.wg_rx_sessions_retire(self.ctx, indices.data_ptr() if indices.shape[0] else None,
+                                                indices.shape[0], n_retired.data_ptr() if n_retired is not None else None,
+                                                stream if stream is not None else _torch_stream()))
+
+    def rx_sessions_count(self) -> tuple[int, int]:
+        """wg_rx_sessions_count: (live, retired) entries of the session table, after everything queued."""
+        live, retired = ctypes.c_uint32(), ctypes.c_uint32()
+        L.check(self._lib.wg_rx_sessions_count(self.ctx, ctypes.byref(live), ctypes.byref(retired)))
+        return live.value, retired.value
+
+    def hs_install(self, entries, summary_n, send_slot, recv_slot, inst_status, summary, slot_first: int,
+                   slot_count: int, source: int, receivers=None, wipe: bool = True, stream: int | None = None) -> None:
+        """wg_hs_install over torch tensors: entries uint8 [n, 176] as hs_respond() wrote its sessions (source
+        WG_HS_INSTALL_SESSIONS) or [n, 96] as hs_finish() wrote established (WG_HS_INSTALL_ESTABLISHED); summary_n
+        that call's summary, int32 [4], whose n_ok is read on the device (None: all n entries); send_slot /
+        recv_slot int32 [n_slots], the key slots by position (sessions[j].init / established[j].pending);
+        inst_status int32 [n] (WG_HS_INST_*); summary int32 [4] (n_ok, n_badslot, n_dup, n_full); [slot_first,
+        slot_first + slot_count) the key slots the call may write (seal1 / open1 / the queues refuse them
+        afterwards); receivers the int32 table of set_receivers(), or None; wipe zeroes the installed entries'
+        keys. Needs rx_sessions_reserve(). The next tx_plan / rx_plan on the same stream uses the sessions."""
+        n_entries = summary_n.data_ptr() if summary_n is not None else None  # n_ok is the summaries' first word
+        b = L.WgHsInstallBatch(entries.data_ptr(), n_entries, send_slot.data_ptr() if send_slot.shape[0] else None,
+                               recv_slot.data_ptr() if recv_slot.shape[0] else None,
+                               receivers.data_ptr() if receivers is not None else None, inst_status.data_ptr(),
+                               summary.data_ptr(), entries.shape[0], send_slot.shape[0], slot_first, slot_count, source,
+                               L.WG_HS_INSTALL_WIPE if wipe else 0)
+        L.check(self._lib.wg_hs_install(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
     def rx_plan(self, wire, pkt_off, pkt_len, desc_out, rx_status, host_list, summary, max_len: int,
                 packed: bool = False, pt_base: int = 0, pt_size: int = 0, stream: int | None = None) -> None:
         """wg_rx_plan over torch tensors: wire uint8 UDP ring, pkt_off int64 [n], pkt_len int32 [n], desc_out
