@@ -997,6 +997,95 @@ int wg_hs_psks_set(wg_ctx* ctx, const uint8_t* psks_host /* 32 n bytes */, uint3
 int wg_hs_initiate(wg_ctx* ctx, const wg_hs_initiate_batch* batch, void* stream);
 int wg_hs_finish(wg_ctx* ctx, const wg_hs_finish_batch* batch, void* stream);
 
+/* ---- the initiations' timestamps, opened on the device; replays refused ----
+ * One captured 148-byte initiation of a known peer, sent again, passes mac1 and authenticates in wg_hs_open; it then
+ * costs wg_hs_respond three ladders and five HKDFs, and wg_hs_install two key slots and a receiver-index entry,
+ * every time. WireGuard's defence is the TAI64N timestamp sealed under the static-static key: a responder answers
+ * an initiation only if its timestamp is greater than the greatest seen from that peer. The reference never opens
+ * the timestamp (Handshakes.java:233-234) and has no such rule: like the replay window and cryptokey routing, this
+ * is a protection the library ADDS, and there is nothing in the reference to be bit-exact with beyond the chain
+ * that sealed the bytes (Handshakes.java:99-105, wg_hs_initiate). wg_hs_stamp sits between wg_hs_open and
+ * wg_hs_respond. For entry j, with r = inits[j].record, p = inits[j].peer, E / es / ets = records[r].msg[8 .. 40) /
+ * [40 .. 88) / [88 .. 116), ss = shared[32 r .. 32 r + 32), ss_p = the peer table's stored X25519(S_priv, S_p), and
+ * H, KDFn, CK0, H0 as above:
+ *     h  = H(H(H(H0 || S_pub) || E) || es)
+ *     ck = KDF1(KDF1(CK0, E), ss)
+ *     k  = KDF2(ck, ss_p)
+ *     T  = ChaCha20-Poly1305-open(k, nonce 0^12, aad = h, ets)     (12 bytes; all 16 tag bytes compared, no early exit)
+ *   This is wg_hs_open's chain once more (28 compressions): the key comes from the ck BEFORE the static-static step
+ *   and the aad is the h before the last mix, and wg_hs_init, whose layout is fixed, carries only the final two. es is
+ *   hashed, not verified again. T is read as ONE unsigned 96-bit big-endian number (memcmp order), which suits
+ *   standard TAI64N and the reference's Crypto.TAI64N() (Crypto.java:19-27) alike.
+ *
+ * wg_hs_stamp(ctx, b, stream): for every j < min(*n_inits, n) (n_inits: a device pointer, usually
+ *   &wg_hs_open_summary.n_emitted; NULL: all n), in this order:
+ *   1. p == WG_HS_NOPEER: WG_HS_TS_NOPEER (no static-static secret on the device; the host finishes that chain
+ *   itself, and the entry stays in inits for it). 2. p >= the table's count, r >= n_rec, or records[r].len != 148:
+ *   WG_HS_TS_BADDESC. 3. the tag does not verify: WG_HS_TS_BADAUTH. 4. T <= stored[p], the peer's value at the START
+ *   of the call: WG_HS_TS_REPLAY (an all-zero T is therefore never accepted). 5. among the entries of this call that
+ *   passed 1-3 and have the same p, another has a greater T, or an equal T at a lower j: WG_HS_TS_SUPERSEDED.
+ *   6. WG_HS_TS_OK, and stored[p] = T.
+ *   Answering only the newest initiation of a peer leaves the same stored value and the same final session as
+ *   WireGuard's one-by-one rule (accept iff T > stored, then stored = T) over the batch in arrival order; it spends
+ *   no ladders on initiations that the next one overrides, and it depends on no dispatch order.
+ *   ts_status[j] and opened[12 j .. 12 j + 12) are written for every covered j and nothing behind them: opened holds
+ *   T where the tag verified (steps 4-6) and 12 zero bytes otherwise. fresh[0 .. n_ok) is the stable compaction of
+ *   the OK entries, each a byte-for-byte copy of its 144-byte wg_hs_init; nothing behind n_ok entries is touched.
+ *   summary = {n_ok, n_stale (REPLAY + SUPERSEDED), n_badauth, n_skipped (NOPEER + BADDESC)}.
+ *   wg_hs_respond(inits = fresh, n_inits = &summary->n_ok) then runs as it always has; its sessions' `init` field,
+ *   and so wg_hs_install's position p, is now the position in FRESH: the host's local_index, send_slot and recv_slot
+ *   arrays are by that position. n = 0 is a no-op. Without a private key: WG_ENOKEY. flags or _reserved not 0:
+ *   WG_EINVAL. n or n_rec above 2^30: WG_E2BIG. inits, records, shared, fresh: 16-byte aligned; summary: 8; the
+ *   others: 4. An output that overlaps another output or an input: WG_EINVAL.
+ *
+ * State. Each peer of wg_hs_peers_set's table has 12 bytes of stored timestamp and the selection's scratch words,
+ *   behind a header at a fixed device address: a captured wg_hs_stamp survives a change of the table without
+ *   re-capture. The state is allocated at the first wg_hs_stamp / wg_hs_stamps_set / wg_hs_stamps_get; a context that
+ *   never stamps pays nothing. A capturing stream cannot allocate: the first wg_hs_stamp there is WG_EINVAL, and an
+ *   earlier wg_hs_stamps_set(ctx, 0, 0, NULL), which is valid, is the way to allocate. wg_hs_peers_set resets every
+ *   stamp to zero, as it does the psks, because positions are renumbered; wg_hs_static_set and wg_hs_key_set leave
+ *   them alone. Scratch (16 bytes per entry: T and a state, never k or ck, which do not leave the registers) is
+ *   sized by wg_hs_reserve once the state exists, and the state starts with what was reserved before; a call that
+ *   needs more allocates it, except on a capturing stream (WG_EINVAL: reserve first). wg_ctx_destroy wipes it.
+ *
+ * wg_hs_stamps_set / wg_hs_stamps_get(ctx, first_peer, n, stamps): the stored timestamps of peers [first_peer,
+ *   first_peer + n), 12 bytes each (host pointer), as wg_hs_stamp's `opened` holds them. Synchronous, and ordered
+ *   after everything queued before them, like wg_hs_psks_set. A range past the table's count: WG_ERANGE. A host
+ *   saves the stamps with get and restores them with set across a restart; until it has, every captured initiation
+ *   of the last 2^64 seconds is fresh again.
+ *
+ * Ordering and graphs. Calls on different streams of one context are ordered by the library (they share the stamps
+ *   and the scratch). Seven launches (chain; three of the selection: a 64-bit atomicMax of T's high 8 bytes, a 32-bit
+ *   atomicMax of the low 4 among those that tie, an atomicMin of j among those that still tie; commit; scan; emit),
+ *   whose boundaries give the order: no workgroup waits on another. Every scratch word is written before it is read
+ *   in each call and nothing about a call lives on the host, so a captured plan + check + dh + open + stamp +
+ *   respond + install replays; a replay over the same ring finds every timestamp stale, wg_hs_respond answers
+ *   nothing and consumes no ephemeral. One entry per lane; no branch, address or loop bound depends on ss, ss_p, ck
+ *   or k. T of an authentic message, the tag's outcome, p and r are public. */
+#define WG_HS_TS_OK 0u
+#define WG_HS_TS_REPLAY 1u     /* not greater than the peer's stored timestamp */
+#define WG_HS_TS_SUPERSEDED 2u /* another authentic entry of this peer in the call is newer, or as new and lower */
+#define WG_HS_TS_BADAUTH 3u
+#define WG_HS_TS_NOPEER 4u     /* inits[j].peer == WG_HS_NOPEER: no static-static secret on the device */
+#define WG_HS_TS_BADDESC 5u    /* peer >= the table's count, record >= n_rec, or records[record].len != 148 */
+typedef struct wg_hs_stamp_summary {
+  uint32_t n_ok, n_stale /* REPLAY + SUPERSEDED */, n_badauth, n_skipped /* NOPEER + BADDESC */;
+} wg_hs_stamp_summary;
+typedef struct wg_hs_stamp_batch {
+  const wg_hs_init* inits;      /* device, 16-byte aligned: wg_hs_open's entries */
+  const uint32_t* n_inits;      /* device: &wg_hs_open_summary.n_emitted; NULL: all n */
+  const wg_hs_record* records;  /* device, 16-byte aligned: the records wg_hs_open read (n_rec entries) */
+  const uint8_t* shared;        /* device, 16-byte aligned, 32 n_rec bytes: wg_hs_dh's */
+  uint32_t* ts_status;          /* device, n entries, WG_HS_TS_* */
+  uint8_t* opened;              /* device, 4-byte aligned, 12 n bytes, by position j */
+  wg_hs_init* fresh;            /* device, 16-byte aligned, n entries: what wg_hs_respond takes */
+  wg_hs_stamp_summary* summary; /* device, 16 bytes, 8-byte aligned */
+  uint32_t n, n_rec, flags /* must be 0 */, _reserved;
+} wg_hs_stamp_batch;
+int wg_hs_stamp(wg_ctx* ctx, const wg_hs_stamp_batch* batch, void* stream);
+int wg_hs_stamps_set(wg_ctx* ctx, uint32_t first_peer, uint32_t n, const uint8_t* stamps_host /* 12 n bytes */);
+int wg_hs_stamps_get(wg_ctx* ctx, uint32_t first_peer, uint32_t n, uint8_t* stamps_host /* 12 n bytes */);
+
 /* ---- handshake sessions installed on the device ----
  * What the reference does with a finished handshake (SessionManager.setSession: a new EstablishedSession around a
  * new SymmetricKeypair(send, recv), reachable under its local index through PeerList) for a ring of wg_hs_session

@@ -82,6 +82,12 @@ WG_HS_INST_FULL = 4
 WG_HS_INSTALL_SESSIONS = 0
 WG_HS_INSTALL_ESTABLISHED = 1
 WG_HS_INSTALL_WIPE = 1
+WG_HS_TS_OK = 0
+WG_HS_TS_REPLAY = 1
+WG_HS_TS_SUPERSEDED = 2
+WG_HS_TS_BADAUTH = 3
+WG_HS_TS_NOPEER = 4
+WG_HS_TS_BADDESC = 5
 WG_MAX_FILTERS = 65536
 WG_NO_FILTER = 0xFFFFFFFF
 WG_LEN_INVALID = 0xFFFFFFFF
@@ -280,6 +286,20 @@ class WgHsFinishBatch(ctypes.Structure):
                 ("n", ctypes.c_uint32), ("n_pending", ctypes.c_uint32)]
 
 
+class WgHsStampSummary(ctypes.Structure):
+    """wg_hs_stamp_summary: totals of one wg_hs_stamp call."""
+    _fields_ = [("n_ok", ctypes.c_uint32), ("n_stale", ctypes.c_uint32), ("n_badauth", ctypes.c_uint32),
+                ("n_skipped", ctypes.c_uint32)]
+
+
+class WgHsStampBatch(ctypes.Structure):
+    """wg_hs_stamp_batch: one wg_hs_stamp call (device pointers)."""
+    _fields_ = [("inits", ctypes.c_void_p), ("n_inits", ctypes.c_void_p), ("records", ctypes.c_void_p),
+                ("shared", ctypes.c_void_p), ("ts_status", ctypes.c_void_p), ("opened", ctypes.c_void_p),
+                ("fresh", ctypes.c_void_p), ("summary", ctypes.c_void_p), ("n", ctypes.c_uint32),
+                ("n_rec", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
+
+
 class WgHsInstallSummary(ctypes.Structure):
     """wg_hs_install_summary: totals of one wg_hs_install call."""
     _fields_ = [("n_ok", ctypes.c_uint32), ("n_badslot", ctypes.c_uint32), ("n_dup", ctypes.c_uint32),
@@ -318,6 +338,7 @@ assert ctypes.sizeof(WgX25519Desc) == 32 and ctypes.sizeof(WgHsDhBatch) == 40
 assert ctypes.sizeof(WgHsInit) == 144 and ctypes.sizeof(WgHsOpenSummary) == 16 and ctypes.sizeof(WgHsOpenBatch) == 64
 assert ctypes.sizeof(WgHsSession) == 176 and ctypes.sizeof(WgHsRespondSummary) == 16 and ctypes.sizeof(WgHsRespondBatch) == 64
 assert ctypes.sizeof(WgHsInstallSummary) == 16 and ctypes.sizeof(WgHsInstallBatch) == 80
+assert ctypes.sizeof(WgHsStampSummary) == 16 and ctypes.sizeof(WgHsStampBatch) == 80
 assert ctypes.sizeof(WgPkt) == 32 and ctypes.sizeof(WgAeadDesc) == 64 and ctypes.sizeof(WgPrefix) == 18
 
 # (name, restype, argtypes) for every symbol include/wgaead.h declares
@@ -372,6 +393,9 @@ SIGNATURES = [
     ("wg_hs_psks_set", _I, [_VP, _VP, _U32]),
     ("wg_hs_initiate", _I, [_VP, ctypes.POINTER(WgHsInitiateBatch), _VP]),
     ("wg_hs_finish", _I, [_VP, ctypes.POINTER(WgHsFinishBatch), _VP]),
+    ("wg_hs_stamp", _I, [_VP, ctypes.POINTER(WgHsStampBatch), _VP]),
+    ("wg_hs_stamps_set", _I, [_VP, _U32, _U32, _VP]),
+    ("wg_hs_stamps_get", _I, [_VP, _U32, _U32, _VP]),
     ("wg_rx_sessions_reserve", _I, [_VP, _U32]),
     ("wg_rx_sessions_retire", _I, [_VP, _VP, _U32, _VP, _VP]),
     ("wg_rx_sessions_count", _I, [_VP, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),

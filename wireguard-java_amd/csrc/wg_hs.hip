@@ -49,6 +49,20 @@ struct HsPskHdr {  // at a fixed device address; wg_hs_peers_set and wg_hs_psks_
   uint32_t count, _pad;
 };
 
+struct HsStamp {  // a peer's greatest accepted timestamp: its 12 bytes as one big-endian number (wg_hs_stamp.hip)
+  unsigned long long hi;  // bytes [0, 8)
+  uint32_t lo, _pad;      // bytes [8, 12)
+};
+struct HsStampSel {  // the selection's scratch words of a peer: the greatest candidate of the call, and its lowest entry
+  unsigned long long hi;
+  uint32_t lo, j;
+};
+struct HsStampHdr {  // at a fixed device address; wg_hs_peers_set rewrites it (and may move what it names)
+  HsStamp* stored;
+  HsStampSel* sel;
+  uint32_t count, _pad;
+};
+
 struct HsState {
   // [0, 32) the mac1 key, [32, 64) H(H0 || static public key), [64, 96) the static public key (wg_hs_static_set)
   // (fixed address)
@@ -66,6 +80,11 @@ struct HsState {
   // (64 B), per range its counts; wg_hs_finish's established entries (96 B per record) and its table of pending
   // positions
   DevBuf d_pskhdr, d_ppsk, d_ilad, d_ipart, d_fres, d_ftab;
+  // wg_hs_stamp.hip, allocated at the first wg_hs_stamp* call (has_stamps): the stamps' header (fixed address), per
+  // peer the stored timestamp and the selection's words, per entry {T, state} (16 B), per range its counts
+  DevBuf d_shdr, d_stamps, d_ssel, d_sres, d_spart;
+  bool has_stamps = false;
+  uint32_t reserved = 0;  // the greatest wg_hs_reserve so far: what the stamp's scratch starts with
   uint32_t n_peers = 0;
   bool has_key = false;
   bool has_priv = false;
@@ -77,6 +96,7 @@ const PlanWords kHsOpenWords{"handshake open", "records", "wg_hs_reserve"};
 const PlanWords kHsRespWords{"handshake respond", "entries", "wg_hs_reserve"};
 const PlanWords kHsInitWords{"handshake initiate", "entries", "wg_hs_reserve"};
 const PlanWords kHsFinWords{"handshake finish", "records", "wg_hs_reserve"};
+const PlanWords kHsStampWords{"handshake stamp", "entries", "wg_hs_reserve"};
 
 // The handshake state, allocated at the first wg_hs_* call. Caller holds c->mu.
 int hs_get(wg_ctx* c, HsState** out) {
@@ -115,7 +135,8 @@ void hs_free(wg_ctx* c) {
     if (t->d_priv.p) (void)hipMemsetAsync(t->d_priv.p, 0, 32, c->stream);
     // the peers' static-static secrets, what the last open derived from them, and the last respond's scratch; the
     // psks and the last initiate's and finish's scratch
-    for (DevBuf* b : {&t->d_psec, &t->d_pin, &t->d_ores, &t->d_rlad, &t->d_rres, &t->d_ppsk, &t->d_ilad, &t->d_fres})
+    // (the stamp's scratch holds timestamps and states, never k or ck, which stay in registers: wiped all the same)
+    for (DevBuf* b : {&t->d_psec, &t->d_pin, &t->d_ores, &t->d_rlad, &t->d_rres, &t->d_ppsk, &t->d_ilad, &t->d_fres, &t->d_sres})
       if (b->p) (void)hipMemsetAsync(b->p, 0, b->cap, c->stream);
     (void)hipStreamSynchronize(c->stream);
   }
@@ -175,11 +196,24 @@ int hs_init_grow(HsState* t, uint32_t n, uint32_t n_pending) {
   return t->d_ftab.ensure((size_t)hs_fin_capacity(n_pending) * 4);
 }
 
+// the scratch of wg_hs_stamp for n entries (16 B per entry, per range its counts), and its growth; a context that
+// has never stamped has none
+bool hs_stamp_fits(const HsState* t, uint32_t n) {
+  return !t->has_stamps || ((size_t)std::max(rank_blocks(n), 1u) * 16 <= t->d_spart.cap && (size_t)std::max(n, 1u) * 16 <= t->d_sres.cap);
+}
+int hs_stamp_grow(HsState* t, uint32_t n) {
+  if (!t->has_stamps) return WG_OK;
+  int rc;
+  if ((rc = t->d_spart.ensure((size_t)std::max(rank_blocks(n), 1u) * 16)) != WG_OK) return rc;
+  return t->d_sres.ensure((size_t)std::max(n, 1u) * 16);
+}
+
 int hs_begin(HsState* t, hipStream_t s, bool capturing, uint32_t n, bool open, const PlanWords& w) {
   return plan_begin(t->order, s, capturing, hs_scratch_fits(t, n, open), [&] { return hs_scratch_grow(t, n, open); }, w, n);
 }
 
 int hs_open_rekey(wg_ctx* c, HsState* t, const uint8_t* static_public);  // wg_hs_open.hip
+int hs_stamp_peers_reset(wg_ctx* c, HsState* t);                          // wg_hs_stamp.hip
 
 // The buffers of a call (wg_hs_open, wg_hs_respond): an empty range overlaps nothing.
 struct HsRange {
@@ -537,11 +571,15 @@ int wg_hs_reserve(wg_ctx* c, uint32_t max_messages) {
   int rc;
   if ((rc = hs_get(c, &t)) != WG_OK) return rc;
   const uint32_t pend = std::min(max_messages, 0x10000000u);  // (wg_hs_finish takes no more pending entries)
-  return plan_reserve(hs_scratch_fits(t, max_messages, true) && hs_resp_fits(t, max_messages) && hs_init_fits(t, max_messages, pend), [&] {
-    int grc = hs_scratch_grow(t, max_messages, true);
-    if (grc == WG_OK) grc = hs_resp_grow(t, max_messages);
-    return grc != WG_OK ? grc : hs_init_grow(t, max_messages, pend);
-  });
+  t->reserved = std::max(t->reserved, max_messages);
+  return plan_reserve(hs_scratch_fits(t, max_messages, true) && hs_resp_fits(t, max_messages) && hs_init_fits(t, max_messages, pend) &&
+                          hs_stamp_fits(t, max_messages),
+                      [&] {
+                        int grc = hs_scratch_grow(t, max_messages, true);
+                        if (grc == WG_OK) grc = hs_resp_grow(t, max_messages);
+                        if (grc == WG_OK) grc = hs_stamp_grow(t, max_messages);
+                        return grc != WG_OK ? grc : hs_init_grow(t, max_messages, pend);
+                      });
 }
 
 int wg_hs_check(wg_ctx* c, const wg_hs_batch* b, void* stream) {

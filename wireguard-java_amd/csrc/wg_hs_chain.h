@@ -1,6 +1,6 @@
 // wg_hs_chain.h — the Noise chains of the handshake as data: the step record, its enums, the builders and the
-// programs of k_hs_open (wg_hs_open.hip), k_hs_resp_chain (wg_hs_respond.hip) and the initiator's k_hs_init_chain
-// and k_hs_fin_chain (wg_hs_initiate.hip). Included by wg_hs_chain.hip, which holds the machine that runs them. A
+// programs of k_hs_open (wg_hs_open.hip), k_hs_resp_chain (wg_hs_respond.hip), the initiator's k_hs_init_chain
+// and k_hs_fin_chain (wg_hs_initiate.hip) and k_hs_stamp_chain (wg_hs_stamp.hip). Included by wg_hs_chain.hip, which holds the machine that runs them. A
 // host compiler reads this file too: tests/test_hs_chain.py and tests/test_hs_initiate.py print the programs and
 // run them through a Python interpreter of the operations against the models, so a wrong table fails without a
 // GPU.
@@ -47,6 +47,9 @@ enum Op : uint8_t {
   OP_ITS,     // the AEAD seal of the timestamp under st; H(h || encrypted_timestamp)
   OP_IMAC1B,  // mac1's message, initiation[0 .. 64)
   OP_IMAC1C,  // ... and initiation[64 .. 116)
+  // k_hs_stamp_chain's own (wg_hs_stamp.hip; it has its own OP_H0 and OP_ES2 too, over the same bytes)
+  OP_SES1,  // H(h || encrypted_static), first block, and nothing else: encrypted_static was opened by k_hs_open
+  OP_STS,   // the AEAD open of encrypted_timestamp under st (OP_ITS's mirror); H(h || encrypted_timestamp)
 };
 
 enum Src : uint8_t {
@@ -153,6 +156,19 @@ WG_HSC_DEVICE constexpr Step kFinProgram[] = {
     WG_HSC_EXPANDN(SRC_CK, 2, DST_X),
 };
 
+// k_hs_stamp_chain: k_hs_open's chain again up to the timestamp's key, which wg_hs_init does not carry.
+// h = H(H(H0 || S_pub) || E); ck = KDF1(CK0, E); ck = KDF1(ck, ss) (no k: encrypted_static is not opened a second
+// time); h = H(h || encrypted_static); k = KDF2(ck, static-static) (left in st for the open of the timestamp)
+// and ck = KDF1; h = H(h || encrypted_timestamp), which ends at wg_hs_init's hash.
+WG_HSC_DEVICE constexpr Step kStampProgram[] = {
+    {OP_H0, SRC_ZERO, 0, DST_H},
+    {OP_IN32, SRC_E, 0, DST_NONE}, {OP_OUT, SRC_ZERO, 0, DST_X}, WG_HSC_EXPAND1(DST_CK),
+    WG_HSC_EXTRACT(SRC_SS), WG_HSC_EXPAND1(DST_CK),
+    {OP_SES1, SRC_ZERO, 0, DST_NONE}, {OP_ES2, SRC_ZERO, 0, DST_H},
+    WG_HSC_EXTRACT(SRC_STATIC), WG_HSC_EXPAND1(DST_CK), WG_HSC_EXPANDN(SRC_CK, 2, DST_NONE),
+    {OP_STS, SRC_ZERO, 0, DST_H},
+};
+
 constexpr uint32_t kOpenSteps = sizeof(kOpenProgram) / sizeof(Step);
 constexpr uint32_t kRespSteps = sizeof(kRespProgram) / sizeof(Step);
 static_assert(sizeof(Step) == 4, "a step is one 32-bit word");
@@ -162,6 +178,8 @@ constexpr uint32_t kInitSteps = sizeof(kInitProgram) / sizeof(Step);
 constexpr uint32_t kFinSteps = sizeof(kFinProgram) / sizeof(Step);
 static_assert(kInitSteps == 35, "k_hs_init_chain: 35 compressions");
 static_assert(kFinSteps == 47, "k_hs_fin_chain: 47 compressions");
+constexpr uint32_t kStampSteps = sizeof(kStampProgram) / sizeof(Step);
+static_assert(kStampSteps == 28, "k_hs_stamp_chain: 28 compressions");
 
 // the first step of `op` in a program
 template <uint32_t N>

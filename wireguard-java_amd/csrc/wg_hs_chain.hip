@@ -1,5 +1,5 @@
-// wg_hs_chain.hip — the machine that k_hs_open, k_hs_resp_chain, k_hs_init_chain and k_hs_fin_chain run their
-// Noise chains on (included by wg_capi.hip before wg_hs_open.hip). The chains themselves are data: wg_hs_chain.h.
+// wg_hs_chain.hip — the machine that k_hs_open, k_hs_resp_chain, k_hs_init_chain, k_hs_fin_chain and
+// k_hs_stamp_chain run their Noise chains on (included by wg_capi.hip before wg_hs_open.hip). The chains themselves are data: wg_hs_chain.h.
 //
 // A chain is a row of dependent BLAKE2s compressions per lane, nearly all of them parts of HMAC-BLAKE2s: an
 // HMAC is four compressions (the two key blocks K ^ 0x36.., K ^ 0x5c.. as words, never bytes; the message

@@ -385,6 +385,10 @@ int wg_hs_peers_set(wg_ctx* c, const uint8_t* publics, uint32_t n) {
   HIPTRY(hipMemcpyAsync(t->d_phdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream));
   HIPTRY(hipMemcpyAsync(t->d_pskhdr.p, &K, sizeof K, hipMemcpyHostToDevice, c->stream));
   HIPTRY(hipStreamSynchronize(c->stream));
+  if (t->has_stamps) {  // positions are renumbered: every stored timestamp is zero again
+    const int src = hs_stamp_peers_reset(c, t);
+    if (rc == WG_OK) rc = src;
+  }
   return rc;
 }
 

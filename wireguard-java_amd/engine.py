@@ -740,6 +740,82 @@ class Engine:
             torch.cuda.synchronize(dev)
         return status, est
 
+    # ---- the initiations' timestamps (wg_hs_stamp / wg_hs_stamps_set / wg_hs_stamps_get) --------
+    def hs_stamps_set(self, first_peer: int, stamps) -> None:
+        """wg_hs_stamps_set: the stored timestamps of peers [first_peer, first_peer + n) (12 n bytes, or a sequence
+        of 12-byte timestamps), as hs_stamps_get() returned them before a restart. An empty sequence only allocates
+        the stamps' state, which a capturing stream cannot do."""
+        if not isinstance(stamps, (bytes, bytearray, memoryview, np.ndarray)):
+            stamps = b"".join(bytes(t) for t in stamps)
+        ts = np.frombuffer(bytes(stamps), np.uint8).copy()
+        if ts.size % 12:
+            raise L.WgError(L.WG_EINVAL, f"{ts.size} bytes of timestamps: not a multiple of 12")
+        L.check(self._lib.wg_hs_stamps_set(self.ctx, first_peer, ts.size // 12, ts.ctypes.data if ts.size else None))
+
+    def hs_stamps_get(self, first_peer: int, n: int) -> list:
+        """wg_hs_stamps_get: the stored timestamps of peers [first_peer, first_peer + n), 12 bytes each (all zero:
+        nothing accepted from that peer yet)."""
+        out = np.zeros(12 * n, np.uint8)
+        L.check(self._lib.wg_hs_stamps_get(self.ctx, first_peer, n, out.ctypes.data if n else None))
+        raw = out.tobytes()
+        return [raw[12 * k:12 * k + 12] for k in range(n)]
+
+    def hs_stamp(self, inits, open_summary, records, shared, ts_status, opened, fresh, stamp_summary,
+                 stream: int | None = None) -> None:
+        """wg_hs_stamp over torch tensors: inits uint8 [n, 144] and open_summary int32 [4] as hs_open() wrote them
+        (the entry count, n_emitted, is read on the device: open and stamp run back to back on one stream;
+        open_summary None: all n entries), records uint8 [n_rec, 160] and shared uint8 [n_rec, 32] or [n_rec * 32]
+        as hs_open() read them, ts_status int32 [n] (WG_HS_TS_*), opened uint8 [n, 12] or [n * 12] (the opened
+        timestamps, by position), fresh uint8 [n, 144] (the fresh entries, compacted: what hs_respond() takes, with
+        stamp_summary in open_summary's place), stamp_summary int32 [4] (n_ok, n_stale, n_badauth, n_skipped)."""
+        n_inits = open_summary.data_ptr() + L.WgHsOpenSummary.n_emitted.offset if open_summary is not None else None
+        n_rec = records.shape[0]
+        b = L.WgHsStampBatch(inits.data_ptr(), n_inits, records.data_ptr() if n_rec else None,
+                             shared.data_ptr() if n_rec else None, ts_status.data_ptr(), opened.data_ptr(),
+                             fresh.data_ptr(), stamp_summary.data_ptr(), inits.shape[0], n_rec, 0, 0)
+        L.check(self._lib.wg_hs_stamp(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def hs_stamp_host(self, init_entry, record, shared):
+        """One wg_hs_init entry (a WG_HS_INIT_DTYPE scalar, as hs_open_host() returned it) with the record it came
+        from (a WG_HS_RECORD_DTYPE scalar, or the 148-byte initiation) and wg_hs_dh's 32 bytes for it, through
+        hs_stamp: returns (WG_HS_TS_* status, the 12 opened bytes, or None when the tag did not verify). The
+        entry's `record` field is taken as 0. An OK status has stored the timestamp as the peer's. The device copy
+        of the shared secret is zeroed before it returns. For the noise mirror and tests."""
+        import torch
+        if len(shared) != 32:
+            raise L.WgError(L.WG_EINVAL, "a shared secret is 32 bytes")
+        dev = torch.device("cuda", self.device)
+        rec = np.zeros(1, WG_HS_RECORD_DTYPE)
+        if isinstance(record, (bytes, bytearray, memoryview)):
+            if len(record) != L.WG_HS_INIT_SIZE:
+                raise L.WgError(L.WG_EINVAL, "an initiation is 148 bytes")
+            rec["len"] = L.WG_HS_INIT_SIZE
+            rec["msg"][0] = np.frombuffer(bytes(record), np.uint8)
+        else:
+            rec[0] = record
+        ent = np.zeros(1, WG_HS_INIT_DTYPE)
+        ent[0] = init_entry
+        ent["record"] = 0
+        d_init = torch.from_numpy(ent.view(np.uint8).reshape(1, 144)).to(dev)
+        d_rec = torch.from_numpy(rec.view(np.uint8).reshape(1, 160)).to(dev)
+        d_sh = torch.from_numpy(np.frombuffer(bytes(shared), np.uint8).copy()).to(dev)
+        d_st = torch.zeros(1, dtype=torch.int32, device=dev)
+        d_ts = torch.zeros(12, dtype=torch.uint8, device=dev)
+        d_fresh = torch.zeros((1, 144), dtype=torch.uint8, device=dev)
+        d_sum = torch.zeros(4, dtype=torch.int32, device=dev)
+        st = _torch_stream()
+        try:
+            self.hs_stamp(d_init, None, d_rec, d_sh, d_st, d_ts, d_fresh, d_sum, stream=st)
+            self.sync(st)
+            status = int(d_st.cpu().numpy()[0])
+            opened = d_ts.cpu().numpy().tobytes()
+        finally:
+            d_sh.zero_()
+            d_init.zero_()
+            d_fresh.zero_()
+            torch.cuda.synchronize(dev)
+        return status, (opened if status in (L.WG_HS_TS_OK, L.WG_HS_TS_REPLAY, L.WG_HS_TS_SUPERSEDED) else None)
+
     def set_receivers(self, receivers) -> None:
         """wg_ctx_set_receivers: device tensor of receiver_index per key slot for
         seal(..., frame=True) — contiguous, 4-byte integers, on this engine's device, at

@@ -42,6 +42,36 @@ class Handshakes:
         return NoisePublicKey(init["remote_static"].tobytes())
 
     @staticmethod
+    def openTimestamp(localKeypair: NoisePrivateKey, remoteEphemeral: NoisePublicKey, encryptedStatic,
+                      encryptedTimestamp, engine: Engine | None = None) -> bytes:
+        """The 12 bytes the initiator sealed as its timestamp, or AEADBadTagException when encryptedStatic or
+        encryptedTimestamp does not verify. This mirrors NOTHING in the reference, whose responder mixes
+        encryptedTimestamp into the hash unopened (Handshakes.java:233-234): it is the responder's state of
+        decryptRemoteStatic taken one step further, through wg_hs_dh + wg_hs_open + wg_hs_stamp. localKeypair
+        becomes the engine's static key and the initiator's static key its one peer, whose stored timestamp
+        starts at zero: the call opens, it does not judge freshness (Engine.hs_stamp over a ring does)."""
+        eng = engine or default_engine()
+        eng.hs_static_set(localKeypair.data())
+        fields = (remoteEphemeral.data(), _bytes(encryptedStatic), _bytes(encryptedTimestamp))
+        status, init = eng.hs_open_host(*fields)
+        if status == L.WG_HS_OPEN_BADAUTH:
+            raise AEADBadTagException("Tag mismatch")
+        if init is None:
+            raise L.WgError(L.WG_EINVAL, f"wg_hs_open status {status}")
+        eng.hs_peers_set([init["remote_static"].tobytes()])
+        status, init = eng.hs_open_host(*fields)
+        if status != L.WG_HS_OPEN_OK:
+            raise L.WgError(L.WG_EINVAL, f"wg_hs_open status {status}")
+        (ss, _), = eng.x25519_host([(localKeypair.data(), remoteEphemeral.data())])
+        msg = (bytes([1, 0, 0, 0, 0, 0, 0, 0]) + b"".join(bytes(f) for f in fields)).ljust(L.WG_HS_INIT_SIZE, b"\0")
+        ts_status, opened = eng.hs_stamp_host(init, msg, ss)
+        if ts_status == L.WG_HS_TS_BADAUTH:
+            raise AEADBadTagException("Tag mismatch")
+        if opened is None:
+            raise L.WgError(L.WG_EINVAL, f"wg_hs_stamp status {ts_status}")
+        return opened
+
+    @staticmethod
     def responderHandshake(localKeypair: NoisePrivateKey, remoteEphemeral: NoisePublicKey, encryptedStatic,
                            encryptedTimestamp, engine: Engine | None = None, ephemeral=None,
                            localIndex: int = 0) -> "ResponderHandshake":
