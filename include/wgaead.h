@@ -559,7 +559,8 @@ int wg_rx_deliver(wg_ctx* ctx, const wg_rx_deliver_batch* batch, void* stream);
  * tests them where they lie and compacts the accepted ones into records, so the host copies back
  * 16 + 160 n_valid bytes and starts Noise on those; it never fetches the ring. The initiations' static DH
  * and the open of their encrypted static follow in the next two sections; the rest of the Noise state
- * machine, cookies and timers stay on the host.
+ * machine and its timers stay on the host. wg_hs_admit ("cookie replies and mac2 under load" below) is the
+ * same check for a responder that demands cookies.
  *
  * wg_blake2s_batch(ctx, desc, n, in, in_size, out, out_size, status, stream): BLAKE2s (RFC 7693),
  *   sequential mode, fanout 1, depth 1, parameter word outlen | keylen << 8 | 0x01010000
@@ -1085,6 +1086,168 @@ typedef struct wg_hs_stamp_batch {
 int wg_hs_stamp(wg_ctx* ctx, const wg_hs_stamp_batch* batch, void* stream);
 int wg_hs_stamps_set(wg_ctx* ctx, uint32_t first_peer, uint32_t n, const uint8_t* stamps_host /* 12 n bytes */);
 int wg_hs_stamps_get(wg_ctx* ctx, uint32_t first_peer, uint32_t n, uint8_t* stamps_host /* 12 n bytes */);
+
+/* ---- cookie replies and mac2 under load, on the device ----
+ * mac1 needs only our public key, and wg_hs_stamp stops captured initiations, not fresh ones: a sender that never
+ * proved it owns its source address still costs a ladder and the open chain per message. WireGuard's answer is the
+ * cookie. A responder under load answers a valid-mac1 message whose mac2 does not verify with a 64-byte type-3
+ * reply that carries a MAC of the sender's source address, sealed so that only the sender of THAT message can open
+ * it; the sender repeats its message with mac2 keyed by the cookie, and only then is the ladder spent. The reference
+ * has none of this (IncomingInitiation.java:38-40), wg_hs_check keeps the reference's rule (mac2 all zero) bit for
+ * bit, and these calls are what the library ADDS, as it added wg_hs_stamp. With MAC(k, m) = BLAKE2s-128 keyed with
+ * k, and H = BLAKE2s-256:
+ *     Kc(P)       = H("cookie--" || P)                          for a static public key P (one compression)
+ *     cookie(src) = MAC(secret, A)      A = addr[0 .. 4) || port (family 4, 6 bytes), addr[0 .. 16) || port (family 6,
+ *                                       18 bytes); the port's 2 bytes in network order
+ *     mac2        = MAC(cookie, msg[0 .. L - 16))                the 16-byte cookie is the key
+ *     XAEAD(K, nonce24, pt, aad): sub = HChaCha20(K, nonce24[0 .. 16)) (the 20 ChaCha rounds over {constants, K,
+ *                   nonce16} without the final addition; state words 0-3 and 12-15), then RFC 8439
+ *                   ChaCha20-Poly1305 under sub with the nonce 0^4 || nonce24[16 .. 24)
+ *                   (draft-irtf-cfrg-xchacha-03). Here pt is the 16-byte cookie and aad the message's 16-byte mac1.
+ *     reply (64 B) = {3, 0,0,0, receiver = the message's sender index msg[4 .. 8), nonce[24],
+ *                     XAEAD(Kc(the replier's static public key), nonce, cookie, aad = msg's mac1)[32]}
+ *
+ * wg_hs_cookie_secret_set(ctx, secret): the responder's 32-byte secret (host pointer), from the host's CSPRNG. The
+ *   host rotates it by its own clock (WireGuard: every 120 s); the library has no clock. Synchronous, and ordered
+ *   after everything queued before it. The secret sits at a device address that is fixed for the life of the
+ *   context: a captured admit sees a new secret without re-capture. wg_ctx_destroy wipes it. Kc(local static public
+ *   key) is derived on the device by wg_hs_key_set (and wg_hs_static_set), in the launch that derives the mac1 key.
+ *
+ * wg_hs_admit(ctx, b, stream): wg_hs_check under load. b->hs is a wg_hs_batch with the same meaning of every field.
+ *   src: n entries BY BATCH INDEX (8-byte aligned); nonces: 24 bytes per LIST POSITION, fresh from the host's CSPRNG
+ *   (16-byte aligned), input AND output; replies: n entries (16-byte aligned); admit_summary: 8-byte aligned. For
+ *   list position k with i = list[k], steps 1-4 are those of wg_hs_check (bounds, type, exact size, mac1). Then:
+ *   5. src[i].family is neither 4 nor 6: WG_HS_BADSRC.
+ *   6. msg[L - 16 .. L) == MAC(cookie(src[i]), msg[0 .. L - 16)): WG_HS_OK. All 16 bytes are compared, without an
+ *      early exit.
+ *   7. the 24 nonce bytes of position k are all zero: WG_HS_NONONCE; no reply is written.
+ *   8. WG_HS_NEEDCOOKIE: a reply is emitted, and the 24 nonce bytes of position k are overwritten with zeros.
+ *   A message with an all-zero mac2 lands in 7 or 8. hs_status, records and summary are as in wg_hs_check: records is
+ *   the stable compaction of the WG_HS_OK messages and n_rejected counts every other position, NEEDCOOKIE included;
+ *   wg_hs_dh and the rest of the chain run on records unchanged (they never read the MAC fields). replies[0 ..
+ *   n_replies) is the stable compaction, in list order, of the NEEDCOOKIE positions: {index = i, len = 64, msg,
+ *   _pad = 0}; every byte of a written entry is defined and nothing behind n_replies entries is touched.
+ *   admit_summary = {n_replies, n_mac2_ok (= n_valid), n_nononce, n_badsrc}. A consumed nonce is zeroed, as
+ *   wg_hs_initiate zeroes its ephemerals: a replayed graph without fresh nonces sends no reply (every position that
+ *   needs a cookie answers NONONCE), so a nonce is never used twice under one key. n = 0 writes only the two
+ *   summaries (zeros). Without a mac1 key or without a secret: WG_ENOKEY. An output (hs_status, records, summary,
+ *   nonces, replies, admit_summary) that overlaps another output or an input: WG_EINVAL. Limits, alignment and
+ *   scratch follow wg_hs_check: wg_hs_reserve sizes the scratch, and a capturing stream that would have to allocate
+ *   gets WG_EINVAL. Four launches (admit, two scans, emit; the emit seals the replies), no wait between workgroups,
+ *   nothing about a call on the host: a captured plan + admit replays. Streams of one context are ordered by the
+ *   library. Lanes whose mac1 failed (public) skip the cookie and mac2 work.
+ *
+ * wg_hs_cookie_open(ctx, b, stream): the initiator's side. The call scans all n datagrams of the ring itself (the
+ *   plan does not list type 3). sent: wg_hs_initiate's records, aligned by position with pending (n_pending entries
+ *   each); pending is READ ONLY here. For datagram i, o = pkt_off[i], wl = pkt_len[i], in this order:
+ *   1. wl == 0, o > wire_size or wl > wire_size - o: WG_HS_CK_BADLEN. 2. wire[o] != 3: WG_HS_CK_SKIPPED. 3. wl != 64:
+ *   WG_HS_CK_BADLEN. 4. no live pending entry (state == 1 and peer below the table's count) has local_index ==
+ *   msg[4 .. 8): WG_HS_CK_NOPENDING; the lowest position wins a shared index (wg_hs_finish's lookup table, built by
+ *   the call's first two launches). 5. the XAEAD open under Kc(the peer's static public key) with aad =
+ *   sent[p].msg[116 .. 132) fails (all 16 tag bytes compared): WG_HS_CK_BADAUTH, and nothing changes. 6.
+ *   WG_HS_CK_OK: the 16 opened bytes become the peer's cookie. ck_status[n] is by batch index; learned[0 .. n_ok) is
+ *   the stable compaction of the OK datagrams, {index = i, pending = p, peer, 0}; summary = {n_ok, n_nopending,
+ *   n_badauth, n_skipped}. Two OK replies for one peer in one ring: the one with the lowest batch index is stored,
+ *   whatever the dispatch order (an atomicMin per peer, read one launch later). A pending entry is never consumed or
+ *   altered: the handshake goes on with a retransmission. n = 0 is a no-op. Without a private key: WG_ENOKEY. n above 2^30 or
+ *   n_pending above 2^28: WG_E2BIG. learned: 16-byte aligned; summary: 8; ck_status: 4. An output that overlaps
+ *   another output or an input: WG_EINVAL. Scratch as wg_hs_finish (wg_hs_reserve(max(n, n_pending))); it holds the
+ *   opened cookies for the time of the call. Five launches (fill, insert, open, scan, emit).
+ *
+ * The cookie table: one {cookie[16], have} per position of wg_hs_peers_set's table, on the device behind a header at
+ *   a fixed address. wg_hs_cookies_get / wg_hs_cookies_set(ctx, first_peer, n, cookies_host (16 n bytes), have_host
+ *   (n bytes)) read and write it; both synchronous and ordered after everything queued before them; a range past the
+ *   table's count: WG_ERANGE. have = 0 clears an entry (its cookie bytes are stored as zeros): the host expires a
+ *   cookie after 120 s by its own clock. A new peer table clears every cookie, as it resets every psk.
+ *   wg_ctx_destroy wipes the table.
+ *
+ * wg_hs_mac2(ctx, b, stream): after wg_hs_initiate, or over stored records before a retransmission. records is input
+ *   AND output; peer[k] is record k's position in the peer table. For every k < n, in this order: 1. records[k].len is
+ *   neither 148 nor 92: WG_HS_MAC2_BADDESC. 2. peer[k] >= the table's count: WG_HS_MAC2_BADPEER. 3. the peer holds no
+ *   cookie: WG_HS_MAC2_NONE; the record is untouched. 4. WG_HS_MAC2_OK: msg[L - 16 .. L) = MAC(cookie, msg[0 ..
+ *   L - 16)), exactly those 16 bytes. summary = {n_ok, n_none, n_bad (BADDESC + BADPEER), 0}. n = 0 is a no-op. n above
+ *   2^30: WG_E2BIG. records: 16-byte aligned; summary: 8; the others: 4. Two launches (mac2, scan). A captured
+ *   initiate + mac2 replays and follows the table without re-capture.
+ *
+ * For all of these calls, no branch, address or loop bound depends on the secret, a cookie, a cookie key, a subkey or
+ *   a keystream byte; the one exception is the all-zero test of a raw nonce. Source addresses, indices, peer
+ *   positions and the statuses (the comparisons' outcomes among them) are public. Not here: a rate limiter and the
+ *   "under load" decision (the host chooses wg_hs_check or wg_hs_admit per ring), expiry and rotation (the host's
+ *   clock, through the setters), mac2 inside wg_hs_respond's sessions (wg_hs_mac2 takes 92-byte records if the host
+ *   copies them), and type 3 in wg_rx_plan's lists. */
+#define WG_HS_BADSRC 5u     /* wg_hs_admit: src.family is neither 4 nor 6 */
+#define WG_HS_NONONCE 6u    /* wg_hs_admit: a cookie is needed and the position's nonce is all zero */
+#define WG_HS_NEEDCOOKIE 7u /* wg_hs_admit: mac2 does not verify; a cookie reply was emitted */
+#define WG_HS_COOKIE_SIZE 64u
+#define WG_HS_CK_OK 0u
+#define WG_HS_CK_NOPENDING 1u /* no live pending entry has the reply's receiver index */
+#define WG_HS_CK_BADAUTH 2u
+#define WG_HS_CK_SKIPPED 3u /* not a type-3 datagram */
+#define WG_HS_CK_BADLEN 4u  /* datagram out of bounds, or a type-3 datagram that is not 64 bytes */
+#define WG_HS_MAC2_OK 0u
+#define WG_HS_MAC2_NONE 1u    /* the peer holds no cookie */
+#define WG_HS_MAC2_BADDESC 2u /* the record's len is neither 148 nor 92 */
+#define WG_HS_MAC2_BADPEER 3u /* peer[k] is not a position in the peer table */
+typedef struct wg_hs_src { /* 24 bytes; by batch index, filled by the host's receive loop */
+  uint8_t addr[16];        /* IPv4 in addr[0..4) */
+  uint8_t port[2];         /* network order */
+  uint8_t family;          /* 4 or 6 */
+  uint8_t _pad[5];
+} wg_hs_src;
+typedef struct wg_hs_cookie_reply { /* 80 bytes */
+  uint32_t index;                   /* batch index of the datagram it answers */
+  uint32_t len;                     /* 64 */
+  uint8_t msg[64];
+  uint32_t _pad[2];
+} wg_hs_cookie_reply;
+typedef struct wg_hs_admit_summary {
+  uint32_t n_replies, n_mac2_ok, n_nononce, n_badsrc;
+} wg_hs_admit_summary;
+typedef struct wg_hs_admit_batch {
+  wg_hs_batch hs;                     /* as wg_hs_check takes it */
+  const wg_hs_src* src;               /* device, 8-byte aligned, n entries, by batch index */
+  uint8_t* nonces;                    /* device, 16-byte aligned, n * 24 bytes, by list position; in and out */
+  wg_hs_cookie_reply* replies;        /* device, 16-byte aligned, n entries */
+  wg_hs_admit_summary* admit_summary; /* device, 16 bytes, 8-byte aligned */
+} wg_hs_admit_batch;
+typedef struct wg_hs_learned { /* 16 bytes */
+  uint32_t index;              /* batch index of the reply's datagram */
+  uint32_t pending;            /* position in pending (and in sent) */
+  uint32_t peer;
+  uint32_t _zero;
+} wg_hs_learned;
+typedef struct wg_hs_cookie_open_summary {
+  uint32_t n_ok, n_nopending, n_badauth, n_skipped;
+} wg_hs_cookie_open_summary;
+typedef struct wg_hs_cookie_open_batch {
+  const uint8_t* wire;                /* UDP ring (device) */
+  uint64_t wire_size;
+  const uint64_t* pkt_off;            /* device, n entries */
+  const uint32_t* pkt_len;            /* device, n entries */
+  const wg_hs_record* sent;           /* device, 16-byte aligned, n_pending entries: wg_hs_initiate's records */
+  const wg_hs_pending* pending;       /* device, 16-byte aligned, n_pending entries; read only */
+  uint32_t* ck_status;                /* device, n entries, WG_HS_CK_*, by batch index */
+  wg_hs_learned* learned;             /* device, 16-byte aligned, n entries */
+  wg_hs_cookie_open_summary* summary; /* device, 16 bytes, 8-byte aligned */
+  uint32_t n, n_pending;
+} wg_hs_cookie_open_batch;
+typedef struct wg_hs_mac2_summary {
+  uint32_t n_ok, n_none, n_bad /* BADDESC + BADPEER */, _zero;
+} wg_hs_mac2_summary;
+typedef struct wg_hs_mac2_batch {
+  wg_hs_record* records;       /* device, 16-byte aligned, n entries; in and out */
+  const uint32_t* peer;        /* device, n entries */
+  uint32_t* mac2_status;       /* device, n entries, WG_HS_MAC2_* */
+  wg_hs_mac2_summary* summary; /* device, 16 bytes, 8-byte aligned */
+  uint32_t n, _reserved;
+} wg_hs_mac2_batch;
+int wg_hs_cookie_secret_set(wg_ctx* ctx, const uint8_t* secret /* 32 bytes */);
+int wg_hs_admit(wg_ctx* ctx, const wg_hs_admit_batch* batch, void* stream);
+int wg_hs_cookie_open(wg_ctx* ctx, const wg_hs_cookie_open_batch* batch, void* stream);
+int wg_hs_cookies_get(wg_ctx* ctx, uint32_t first_peer, uint32_t n, uint8_t* cookies_host /* 16 n */, uint8_t* have_host /* n */);
+int wg_hs_cookies_set(wg_ctx* ctx, uint32_t first_peer, uint32_t n, const uint8_t* cookies_host /* 16 n */,
+                      const uint8_t* have_host /* n */);
+int wg_hs_mac2(wg_ctx* ctx, const wg_hs_mac2_batch* batch, void* stream);
 
 /* ---- handshake sessions installed on the device ----
  * What the reference does with a finished handshake (SessionManager.setSession: a new EstablishedSession around a

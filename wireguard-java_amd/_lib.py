@@ -49,6 +49,19 @@ WG_HS_BADLEN = 1
 WG_HS_BADTYPE = 2
 WG_HS_BADMAC1 = 3
 WG_HS_BADMAC2 = 4
+WG_HS_BADSRC = 5
+WG_HS_NONONCE = 6
+WG_HS_NEEDCOOKIE = 7
+WG_HS_COOKIE_SIZE = 64
+WG_HS_CK_OK = 0
+WG_HS_CK_NOPENDING = 1
+WG_HS_CK_BADAUTH = 2
+WG_HS_CK_SKIPPED = 3
+WG_HS_CK_BADLEN = 4
+WG_HS_MAC2_OK = 0
+WG_HS_MAC2_NONE = 1
+WG_HS_MAC2_BADDESC = 2
+WG_HS_MAC2_BADPEER = 3
 WG_HS_INIT_SIZE = 148
 WG_HS_RESP_SIZE = 92
 WG_X25519_OK = 0
@@ -300,6 +313,62 @@ class WgHsStampBatch(ctypes.Structure):
                 ("n_rec", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
 
 
+class WgHsSrc(ctypes.Structure):
+    """wg_hs_src: the source address of one datagram (wg_hs_admit)."""
+    _fields_ = [("addr", ctypes.c_uint8 * 16), ("port", ctypes.c_uint8 * 2), ("family", ctypes.c_uint8),
+                ("_pad", ctypes.c_uint8 * 5)]
+
+
+class WgHsCookieReply(ctypes.Structure):
+    """wg_hs_cookie_reply: one cookie reply of wg_hs_admit."""
+    _fields_ = [("index", ctypes.c_uint32), ("len", ctypes.c_uint32), ("msg", ctypes.c_uint8 * 64),
+                ("_pad", ctypes.c_uint32 * 2)]
+
+
+class WgHsAdmitSummary(ctypes.Structure):
+    """wg_hs_admit_summary: the cookie side's totals of one wg_hs_admit call."""
+    _fields_ = [("n_replies", ctypes.c_uint32), ("n_mac2_ok", ctypes.c_uint32), ("n_nononce", ctypes.c_uint32),
+                ("n_badsrc", ctypes.c_uint32)]
+
+
+class WgHsAdmitBatch(ctypes.Structure):
+    """wg_hs_admit_batch: one wg_hs_admit call (device pointers)."""
+    _fields_ = [("hs", WgHsBatch), ("src", ctypes.c_void_p), ("nonces", ctypes.c_void_p), ("replies", ctypes.c_void_p),
+                ("admit_summary", ctypes.c_void_p)]
+
+
+class WgHsLearned(ctypes.Structure):
+    """wg_hs_learned: one opened cookie reply of wg_hs_cookie_open."""
+    _fields_ = [("index", ctypes.c_uint32), ("pending", ctypes.c_uint32), ("peer", ctypes.c_uint32),
+                ("_zero", ctypes.c_uint32)]
+
+
+class WgHsCookieOpenSummary(ctypes.Structure):
+    """wg_hs_cookie_open_summary: totals of one wg_hs_cookie_open call."""
+    _fields_ = [("n_ok", ctypes.c_uint32), ("n_nopending", ctypes.c_uint32), ("n_badauth", ctypes.c_uint32),
+                ("n_skipped", ctypes.c_uint32)]
+
+
+class WgHsCookieOpenBatch(ctypes.Structure):
+    """wg_hs_cookie_open_batch: one wg_hs_cookie_open call (device pointers)."""
+    _fields_ = [("wire", ctypes.c_void_p), ("wire_size", ctypes.c_uint64), ("pkt_off", ctypes.c_void_p),
+                ("pkt_len", ctypes.c_void_p), ("sent", ctypes.c_void_p), ("pending", ctypes.c_void_p),
+                ("ck_status", ctypes.c_void_p), ("learned", ctypes.c_void_p), ("summary", ctypes.c_void_p),
+                ("n", ctypes.c_uint32), ("n_pending", ctypes.c_uint32)]
+
+
+class WgHsMac2Summary(ctypes.Structure):
+    """wg_hs_mac2_summary: totals of one wg_hs_mac2 call."""
+    _fields_ = [("n_ok", ctypes.c_uint32), ("n_none", ctypes.c_uint32), ("n_bad", ctypes.c_uint32),
+                ("_zero", ctypes.c_uint32)]
+
+
+class WgHsMac2Batch(ctypes.Structure):
+    """wg_hs_mac2_batch: one wg_hs_mac2 call (device pointers)."""
+    _fields_ = [("records", ctypes.c_void_p), ("peer", ctypes.c_void_p), ("mac2_status", ctypes.c_void_p),
+                ("summary", ctypes.c_void_p), ("n", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
+
+
 class WgHsInstallSummary(ctypes.Structure):
     """wg_hs_install_summary: totals of one wg_hs_install call."""
     _fields_ = [("n_ok", ctypes.c_uint32), ("n_badslot", ctypes.c_uint32), ("n_dup", ctypes.c_uint32),
@@ -339,6 +408,9 @@ assert ctypes.sizeof(WgHsInit) == 144 and ctypes.sizeof(WgHsOpenSummary) == 16 a
 assert ctypes.sizeof(WgHsSession) == 176 and ctypes.sizeof(WgHsRespondSummary) == 16 and ctypes.sizeof(WgHsRespondBatch) == 64
 assert ctypes.sizeof(WgHsInstallSummary) == 16 and ctypes.sizeof(WgHsInstallBatch) == 80
 assert ctypes.sizeof(WgHsStampSummary) == 16 and ctypes.sizeof(WgHsStampBatch) == 80
+assert ctypes.sizeof(WgHsSrc) == 24 and ctypes.sizeof(WgHsCookieReply) == 80 and ctypes.sizeof(WgHsAdmitSummary) == 16
+assert ctypes.sizeof(WgHsAdmitBatch) == 112 and ctypes.sizeof(WgHsLearned) == 16 and ctypes.sizeof(WgHsCookieOpenSummary) == 16
+assert ctypes.sizeof(WgHsCookieOpenBatch) == 80 and ctypes.sizeof(WgHsMac2Summary) == 16 and ctypes.sizeof(WgHsMac2Batch) == 40
 assert ctypes.sizeof(WgPkt) == 32 and ctypes.sizeof(WgAeadDesc) == 64 and ctypes.sizeof(WgPrefix) == 18
 
 # (name, restype, argtypes) for every symbol include/wgaead.h declares
@@ -396,6 +468,12 @@ SIGNATURES = [
     ("wg_hs_stamp", _I, [_VP, ctypes.POINTER(WgHsStampBatch), _VP]),
     ("wg_hs_stamps_set", _I, [_VP, _U32, _U32, _VP]),
     ("wg_hs_stamps_get", _I, [_VP, _U32, _U32, _VP]),
+    ("wg_hs_cookie_secret_set", _I, [_VP, _VP]),
+    ("wg_hs_admit", _I, [_VP, ctypes.POINTER(WgHsAdmitBatch), _VP]),
+    ("wg_hs_cookie_open", _I, [_VP, ctypes.POINTER(WgHsCookieOpenBatch), _VP]),
+    ("wg_hs_cookies_get", _I, [_VP, _U32, _U32, _VP, _VP]),
+    ("wg_hs_cookies_set", _I, [_VP, _U32, _U32, _VP, _VP]),
+    ("wg_hs_mac2", _I, [_VP, ctypes.POINTER(WgHsMac2Batch), _VP]),
     ("wg_rx_sessions_reserve", _I, [_VP, _U32]),
     ("wg_rx_sessions_retire", _I, [_VP, _VP, _U32, _VP, _VP]),
     ("wg_rx_sessions_count", _I, [_VP, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),

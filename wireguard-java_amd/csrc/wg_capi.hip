@@ -821,6 +821,7 @@ int launch_after_seal(wg_ctx* c, const wg_batch* sb, const wg_batch* ob, hipStre
 #include "wg_hs_initiate.hip"
 #include "wg_hs_install.hip"
 #include "wg_hs_stamp.hip"
+#include "wg_hs_cookie.hip"
 
 extern "C" {
 

@@ -33,6 +33,13 @@ __device__ __forceinline__ uint32_t rotl8(uint32_t x) { return __builtin_amdgcn_
   a += b; d ^= a; d = rotl8(d);          \
   c += d; b ^= c; b = rotl(b, 7);
 
+// The ten double rounds over the state words, in place: what chacha20_block and HChaCha20 (wg_hs_cookie.hip) share.
+#define WG_CHACHA_ROUNDS(x0, x1, x2, x3, x4, x5, x6, x7, x8, x9, x10, x11, x12, x13, x14, x15)             \
+  _Pragma("unroll 2") for (int r = 0; r < 10; ++r) {                                                      \
+    WG_QR(x0, x4, x8, x12) WG_QR(x1, x5, x9, x13) WG_QR(x2, x6, x10, x14) WG_QR(x3, x7, x11, x15)         \
+    WG_QR(x0, x5, x10, x15) WG_QR(x1, x6, x11, x12) WG_QR(x2, x7, x8, x13) WG_QR(x3, x4, x9, x14)         \
+  }
+
 // Keystream block for (key, 32-bit block counter, nonce words n0..n2).
 // out[i] = permute(state)[i] + state[i], i.e. little-endian keystream words.
 __device__ __forceinline__ void chacha20_block(const uint32_t k[8], uint32_t ctr, uint32_t n0, uint32_t n1,
@@ -40,16 +47,22 @@ __device__ __forceinline__ void chacha20_block(const uint32_t k[8], uint32_t ctr
   uint32_t x0 = 0x61707865u, x1 = 0x3320646eu, x2 = 0x79622d32u, x3 = 0x6b206574u;
   uint32_t x4 = k[0], x5 = k[1], x6 = k[2], x7 = k[3], x8 = k[4], x9 = k[5], x10 = k[6], x11 = k[7];
   uint32_t x12 = ctr, x13 = n0, x14 = n1, x15 = n2;
-#pragma unroll 2
-  for (int r = 0; r < 10; ++r) {
-    WG_QR(x0, x4, x8, x12) WG_QR(x1, x5, x9, x13) WG_QR(x2, x6, x10, x14) WG_QR(x3, x7, x11, x15)
-    WG_QR(x0, x5, x10, x15) WG_QR(x1, x6, x11, x12) WG_QR(x2, x7, x8, x13) WG_QR(x3, x4, x9, x14)
-  }
+  WG_CHACHA_ROUNDS(x0, x1, x2, x3, x4, x5, x6, x7, x8, x9, x10, x11, x12, x13, x14, x15)
   out[0] = x0 + 0x61707865u; out[1] = x1 + 0x3320646eu; out[2] = x2 + 0x79622d32u; out[3] = x3 + 0x6b206574u;
   out[4] = x4 + k[0]; out[5] = x5 + k[1]; out[6] = x6 + k[2]; out[7] = x7 + k[3];
   out[8] = x8 + k[4]; out[9] = x9 + k[5]; out[10] = x10 + k[6]; out[11] = x11 + k[7];
   out[12] = x12 + ctr; out[13] = x13 + n0; out[14] = x14 + n1; out[15] = x15 + n2;
 }
+// sub = HChaCha20(k, n16): the rounds without the final addition; state words 0-3 and 12-15
+__device__ __forceinline__ void hchacha20(const uint32_t k[8], const uint32_t n[4], uint32_t sub[8]) {
+  uint32_t x0 = 0x61707865u, x1 = 0x3320646eu, x2 = 0x79622d32u, x3 = 0x6b206574u;
+  uint32_t x4 = k[0], x5 = k[1], x6 = k[2], x7 = k[3], x8 = k[4], x9 = k[5], x10 = k[6], x11 = k[7];
+  uint32_t x12 = n[0], x13 = n[1], x14 = n[2], x15 = n[3];
+  WG_CHACHA_ROUNDS(x0, x1, x2, x3, x4, x5, x6, x7, x8, x9, x10, x11, x12, x13, x14, x15)
+  sub[0] = x0; sub[1] = x1; sub[2] = x2; sub[3] = x3;
+  sub[4] = x12; sub[5] = x13; sub[6] = x14; sub[7] = x15;
+}
+
 // rotl16(d ^ a) as two SDWA xors, one per 16-bit half (the halves swap places):
 // VOP2-SDWA issue instead of v_xor_b32 + v_perm_b32 (tools/microbench6.hip).
 __device__ __forceinline__ uint32_t xor_rotl16_sdwa(uint32_t d, uint32_t a) {
@@ -200,6 +213,7 @@ __device__ __forceinline__ void chacha20_block_full(const uint4* key_lds, uint32
   out[8] = y[8] + kb.x; out[9] = y[9] + kb.y; out[10] = y[10] + kb.z; out[11] = y[11] + kb.w;
   out[12] = y[12] + ctr; out[13] = y[13] + n0; out[14] = y[14] + n1; out[15] = y[15] + n2;
 }
+#undef WG_CHACHA_ROUNDS
 #undef WG_QR
 #undef WG_QR_SDWA
 

@@ -63,8 +63,22 @@ struct HsStampHdr {  // at a fixed device address; wg_hs_peers_set rewrites it (
   uint32_t count, _pad;
 };
 
+struct HsCookie {  // a peer's cookie, learned from its reply (wg_hs_cookie.hip)
+  uint32_t cookie[4];
+  uint32_t have;  // 1: mac2 is written from it
+  uint32_t sel;   // wg_hs_cookie_open's selection: the lowest batch index that opened a reply of this peer; ~0 between calls
+  uint32_t _pad[2];
+};
+struct HsCookieHdr {  // at a fixed device address; wg_hs_peers_set rewrites it (and may move what it names)
+  HsCookie* entries;
+  uint32_t count, _pad;
+};
+
+constexpr size_t kHsKeyBytes = 160;
+
 struct HsState {
-  // [0, 32) the mac1 key, [32, 64) H(H0 || static public key), [64, 96) the static public key (wg_hs_static_set)
+  // [0, 32) the mac1 key, [32, 64) H(H0 || static public key), [64, 96) the static public key (wg_hs_static_set),
+  // [96, 128) the cookie key H("cookie--" || static public key), [128, 160) the cookie secret (wg_hs_cookie.hip)
   // (fixed address)
   DevBuf d_key;
   DevBuf d_priv;   // the static private key, 32 B (fixed address; wg_hs_static_set, wg_x25519.hip)
@@ -84,6 +98,9 @@ struct HsState {
   // peer the stored timestamp and the selection's words, per entry {T, state} (16 B), per range its counts
   DevBuf d_shdr, d_stamps, d_ssel, d_sres, d_spart;
   bool has_stamps = false;
+  // wg_hs_cookie.hip: the cookie table's header (fixed address) and the table of wg_hs_peers_set's peers
+  DevBuf d_chdr, d_cook;
+  bool has_secret = false;
   uint32_t reserved = 0;  // the greatest wg_hs_reserve so far: what the stamp's scratch starts with
   uint32_t n_peers = 0;
   bool has_key = false;
@@ -103,18 +120,22 @@ int hs_get(wg_ctx* c, HsState** out) {
   if (!c->hs) {
     auto t = std::make_unique<HsState>();
     int rc;
-    if ((rc = t->d_key.ensure(96)) != WG_OK || (rc = t->d_priv.ensure(32)) != WG_OK ||
+    if ((rc = t->d_key.ensure(kHsKeyBytes)) != WG_OK || (rc = t->d_priv.ensure(32)) != WG_OK ||
         (rc = t->d_stage.ensure(512)) != WG_OK || (rc = t->d_phdr.ensure(sizeof(HsPeerHdr))) != WG_OK ||
-        (rc = t->d_pempty.ensure(16 * sizeof(uint32_t))) != WG_OK || (rc = t->d_pskhdr.ensure(sizeof(HsPskHdr))) != WG_OK)
+        (rc = t->d_pempty.ensure(16 * sizeof(uint32_t))) != WG_OK || (rc = t->d_pskhdr.ensure(sizeof(HsPskHdr))) != WG_OK ||
+        (rc = t->d_chdr.ensure(sizeof(HsCookieHdr))) != WG_OK)
       return rc;
     HsPeerHdr H{};  // no peers
     H.slots = (const uint32_t*)t->d_pempty.p;
     H.mask = 15u;
     HsPskHdr K{};  // ... and no psks
     K.psks = (const uint8_t*)t->d_pempty.p;
+    HsCookieHdr C{};  // ... and no cookies
+    C.entries = (HsCookie*)t->d_pempty.p;
     hipError_t e = t->order.create();
-    if (e == hipSuccess) e = hipMemsetAsync(t->d_key.p, 0, 96, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t->d_key.p, 0, kHsKeyBytes, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(t->d_pskhdr.p, &K, sizeof K, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(t->d_chdr.p, &C, sizeof C, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(t->d_priv.p, 0, 32, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(t->d_pempty.p, 0, 16 * sizeof(uint32_t), c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(t->d_phdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream);
@@ -131,12 +152,13 @@ void hs_free(wg_ctx* c) {
   HsState* t = c->hs;
   if (t->d_key.p) {  // the keys are wiped, like the key table
     (void)hipDeviceSynchronize();
-    (void)hipMemsetAsync(t->d_key.p, 0, 96, c->stream);
+    (void)hipMemsetAsync(t->d_key.p, 0, kHsKeyBytes, c->stream);  // the cookie key and secret among them
     if (t->d_priv.p) (void)hipMemsetAsync(t->d_priv.p, 0, 32, c->stream);
     // the peers' static-static secrets, what the last open derived from them, and the last respond's scratch; the
     // psks and the last initiate's and finish's scratch
-    // (the stamp's scratch holds timestamps and states, never k or ck, which stay in registers: wiped all the same)
-    for (DevBuf* b : {&t->d_psec, &t->d_pin, &t->d_ores, &t->d_rlad, &t->d_rres, &t->d_ppsk, &t->d_ilad, &t->d_fres, &t->d_sres})
+    // (the stamp's scratch holds timestamps and states, never k or ck, which stay in registers: wiped all the same);
+    // the peers' cookies
+    for (DevBuf* b : {&t->d_psec, &t->d_pin, &t->d_ores, &t->d_rlad, &t->d_rres, &t->d_ppsk, &t->d_ilad, &t->d_fres, &t->d_sres, &t->d_cook})
       if (b->p) (void)hipMemsetAsync(b->p, 0, b->cap, c->stream);
     (void)hipStreamSynchronize(c->stream);
   }
@@ -144,16 +166,17 @@ void hs_free(wg_ctx* c) {
   c->hs = nullptr;
 }
 
-// open: the scratch of wg_hs_open too (per record 112 B of results, per range its counts)
+// open: the scratch of wg_hs_open too (per record 112 B of results, per range its counts). d_part holds two rows
+// of counts: wg_hs_admit ranks records and replies
 bool hs_scratch_fits(const HsState* t, uint32_t n, bool open) {
   const size_t part = (size_t)std::max(rank_blocks(n), 1u) * 16;
-  return part <= t->d_part.cap && (!open || (part <= t->d_opart.cap && (size_t)std::max(n, 1u) * 112 <= t->d_ores.cap));
+  return 2 * part <= t->d_part.cap && (!open || (part <= t->d_opart.cap && (size_t)std::max(n, 1u) * 112 <= t->d_ores.cap));
 }
 // ... and its growth (plan_reserve), for checks (and opens) of up to n messages
 int hs_scratch_grow(HsState* t, uint32_t n, bool open) {
   const size_t part = (size_t)std::max(rank_blocks(n), 1u) * 16;
   int rc;
-  if ((rc = t->d_part.ensure(part)) != WG_OK || !open) return rc;
+  if ((rc = t->d_part.ensure(2 * part)) != WG_OK || !open) return rc;
   if (t->d_ores.p && t->d_ores.cap < (size_t)std::max(n, 1u) * 112) HIPTRY(hipMemset(t->d_ores.p, 0, t->d_ores.cap));  // freed: wiped first
   if ((rc = t->d_opart.ensure(part)) != WG_OK) return rc;
   return t->d_ores.ensure((size_t)std::max(n, 1u) * 112);
@@ -214,6 +237,7 @@ int hs_begin(HsState* t, hipStream_t s, bool capturing, uint32_t n, bool open, c
 
 int hs_open_rekey(wg_ctx* c, HsState* t, const uint8_t* static_public);  // wg_hs_open.hip
 int hs_stamp_peers_reset(wg_ctx* c, HsState* t);                          // wg_hs_stamp.hip
+int hs_cookie_peers_reset(wg_ctx* c, HsState* t);                         // wg_hs_cookie.hip
 
 // The buffers of a call (wg_hs_open, wg_hs_respond): an empty range overlaps nothing.
 struct HsRange {
@@ -463,21 +487,12 @@ __global__ void __launch_bounds__(256) k_hs_check(HsParams P) {
   if (threadIdx.x == 0) P.part[blockIdx.x] = make_uint4(n_valid, n_init, n_resp, n_rej);
 }
 
-// records[prefix of the range + rank in the range] = the accepted message of this list position
-__global__ void __launch_bounds__(256) k_hs_emit(HsParams P) {
-  __shared__ uint32_t s_cnt[4];
-  const uint32_t nl = hs_list_len(P);
-  if (blockIdx.x * kRankRange >= nl) return;  // (workgroup-uniform)
-  const uint32_t k = blockIdx.x * kRankRange + threadIdx.x;
-  const bool ok = k < nl && P.hs_status[k] == WG_HS_OK;
-  const uint4 pre = P.part[blockIdx.x];
-  uint32_t r, total;
-  wgrp::block_rank(ok, s_cnt, r, total);
-  if (!ok) return;
+// records[slot] = the accepted message of list position k
+__device__ __forceinline__ void hs_put_record(const HsParams& P, uint32_t k, uint32_t slot) {
   const uint32_t i = P.list ? P.list[k] : k;
   const uint8_t* msg = P.wire + P.pkt_off[i];
   const uint32_t L = msg[0] == 1u ? 148u : 92u;
-  uint4* rec = (uint4*)(P.records + (pre.x + r));
+  uint4* rec = (uint4*)(P.records + slot);
 #pragma unroll
   for (uint32_t g = 0; g < 10; ++g) {  // 160 B: index, len, 37 message words (zero behind a response), _pad
     uint32_t w[4];
@@ -491,6 +506,20 @@ __global__ void __launch_bounds__(256) k_hs_emit(HsParams P) {
     }
     rec[g] = make_uint4(w[0], w[1], w[2], w[3]);
   }
+}
+
+// records[prefix of the range + rank in the range] = the accepted message of this list position
+__global__ void __launch_bounds__(256) k_hs_emit(HsParams P) {
+  __shared__ uint32_t s_cnt[4];
+  const uint32_t nl = hs_list_len(P);
+  if (blockIdx.x * kRankRange >= nl) return;  // (workgroup-uniform)
+  const uint32_t k = blockIdx.x * kRankRange + threadIdx.x;
+  const bool ok = k < nl && P.hs_status[k] == WG_HS_OK;
+  const uint4 pre = P.part[blockIdx.x];
+  uint32_t r, total;
+  wgrp::block_rank(ok, s_cnt, r, total);
+  if (!ok) return;
+  hs_put_record(P, k, pre.x + r);
 }
 
 }  // namespace wghs
@@ -518,19 +547,26 @@ int b2s_launch(const wg_b2s_desc* desc, uint32_t n, const uint8_t* in, uint64_t 
 // derived). Caller holds c->mu.
 int hs_mac1_key_set(wg_ctx* c, HsState* t, const uint8_t* static_public) {
   int rc;
-  // stage: [0, 32) the descriptor, [32, 72) "mac1----" || public key (InitiationPacket.java:111-115), [96, 100) status
-  uint8_t host[128] = {0};
-  wg_b2s_desc d{};
-  d.in_off = 32;
-  d.len = 40;
-  d.outlen = 32;
-  memcpy(host, &d, sizeof d);
+  // stage: [32, 72) "mac1----" || public key (InitiationPacket.java:111-115), [96, 104) the two statuses;
+  // [384, 448) the two descriptors of the one launch, [448, 488) "cookie--" || public key. The digests go to
+  // [0, 32) and [96, 128) of the key buffer.
+  uint8_t host[128] = {0}, host2[128] = {0};
+  wg_b2s_desc d[2] = {};
+  d[0].in_off = 32;
+  d[1].in_off = 448;
+  d[1].out_off = 96;
+  d[0].len = d[1].len = 40;
+  d[0].outlen = d[1].outlen = 32;
   memcpy(host + 32, "mac1----", 8);
   memcpy(host + 40, static_public, 32);
+  memcpy(host2, d, sizeof d);
+  memcpy(host2 + 64, "cookie--", 8);
+  memcpy(host2 + 72, static_public, 32);
   HIPTRY(hipDeviceSynchronize());  // no check queued earlier (on any stream) may still read the old key
   uint8_t* st = (uint8_t*)t->d_stage.p;
   HIPTRY(hipMemcpyAsync(st, host, sizeof host, hipMemcpyHostToDevice, c->stream));
-  if ((rc = b2s_launch((const wg_b2s_desc*)st, 1, st, 128, (uint8_t*)t->d_key.p, 32, (uint32_t*)(st + 96), c->stream)) != WG_OK)
+  HIPTRY(hipMemcpyAsync(st + 384, host2, sizeof host2, hipMemcpyHostToDevice, c->stream));
+  if ((rc = b2s_launch((const wg_b2s_desc*)(st + 384), 2, st, 512, (uint8_t*)t->d_key.p, 128, (uint32_t*)(st + 96), c->stream)) != WG_OK)
     return rc;
   HIPTRY(hipStreamSynchronize(c->stream));
   t->has_key = true;

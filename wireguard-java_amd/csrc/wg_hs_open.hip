@@ -389,7 +389,8 @@ int wg_hs_peers_set(wg_ctx* c, const uint8_t* publics, uint32_t n) {
     const int src = hs_stamp_peers_reset(c, t);
     if (rc == WG_OK) rc = src;
   }
-  return rc;
+  const int crc = hs_cookie_peers_reset(c, t);  // ... and every cookie is forgotten
+  return rc != WG_OK ? rc : crc;
 }
 
 int wg_hs_open(wg_ctx* c, const wg_hs_open_batch* b, void* stream) {

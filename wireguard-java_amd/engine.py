@@ -50,6 +50,9 @@ WG_HS_PENDING_DTYPE = np.dtype([("state", "<u4"), ("peer", "<u4"), ("local_index
 WG_HS_ESTABLISHED_DTYPE = np.dtype([("index", "<u4"), ("record", "<u4"), ("pending", "<u4"), ("peer", "<u4"),
                                     ("local_index", "<u4"), ("remote_index", "<u4"), ("_zero", "<u4", (2,)),
                                     ("send_key", "u1", (32,)), ("recv_key", "u1", (32,))])
+WG_HS_SRC_DTYPE = np.dtype([("addr", "u1", (16,)), ("port", "u1", (2,)), ("family", "u1"), ("_pad", "u1", (5,))])
+WG_HS_COOKIE_REPLY_DTYPE = np.dtype([("index", "<u4"), ("len", "<u4"), ("msg", "u1", (64,)), ("_pad", "<u4", (2,))])
+WG_HS_LEARNED_DTYPE = np.dtype([("index", "<u4"), ("pending", "<u4"), ("peer", "<u4"), ("_zero", "<u4")])
 
 
 def pack_b2s_desc(in_off, out_off, key_off, length, outlen, keylen) -> np.ndarray:
@@ -774,6 +777,80 @@ class Engine:
                              shared.data_ptr() if n_rec else None, ts_status.data_ptr(), opened.data_ptr(),
                              fresh.data_ptr(), stamp_summary.data_ptr(), inits.shape[0], n_rec, 0, 0)
         L.check(self._lib.wg_hs_stamp(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    # ---- cookies and mac2 under load (wg_hs_cookie_secret_set / wg_hs_admit / wg_hs_cookie_open / wg_hs_mac2) ----
+    def hs_cookie_secret_set(self, secret) -> None:
+        """wg_hs_cookie_secret_set: the responder's 32-byte cookie secret, from the host's CSPRNG; the host rotates
+        it by its own clock (WireGuard: every 120 s)."""
+        sec = np.frombuffer(bytes(secret), np.uint8).copy()
+        if sec.size != 32:
+            raise L.WgError(L.WG_EINVAL, f"cookie secret of {sec.size} bytes")
+        try:
+            L.check(self._lib.wg_hs_cookie_secret_set(self.ctx, sec.ctypes.data))
+        finally:
+            sec[:] = 0
+
+    def hs_admit(self, wire, pkt_off, pkt_len, src, nonces, hs_status, records, hs_summary, replies, admit_summary,
+                 host_list=None, rx_summary=None, stream: int | None = None) -> None:
+        """wg_hs_admit over torch tensors: hs_check() under load. wire / pkt_off / pkt_len / hs_status / records /
+        hs_summary / host_list / rx_summary as hs_check() takes them; src uint8 [n, 24] (wg_hs_src,
+        WG_HS_SRC_DTYPE, by batch index), nonces uint8 [n, 24] or [n * 24] (fresh random bytes by list position;
+        the call zeroes each one it consumed), replies uint8 [n, 80] (wg_hs_cookie_reply,
+        WG_HS_COOKIE_REPLY_DTYPE), admit_summary int32 [4] (n_replies, n_mac2_ok, n_nononce, n_badsrc)."""
+        if (host_list is None) != (rx_summary is None):
+            raise L.WgError(L.WG_EINVAL, "host_list and rx_summary go together")
+        n_list = rx_summary.data_ptr() + L.WgRxSummary.n_host.offset if rx_summary is not None else None
+        hs = L.WgHsBatch(wire.data_ptr(), wire.numel(), pkt_off.data_ptr(), pkt_len.data_ptr(),
+                         host_list.data_ptr() if host_list is not None else None, n_list, hs_status.data_ptr(),
+                         records.data_ptr(), hs_summary.data_ptr(), pkt_off.shape[0], 0)
+        b = L.WgHsAdmitBatch(hs, src.data_ptr(), nonces.data_ptr(), replies.data_ptr(), admit_summary.data_ptr())
+        L.check(self._lib.wg_hs_admit(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def hs_cookie_open(self, wire, pkt_off, pkt_len, sent, pending, ck_status, learned, summary,
+                       stream: int | None = None) -> None:
+        """wg_hs_cookie_open over torch tensors: wire / pkt_off / pkt_len as rx_plan() took them (every datagram is
+        looked at), sent uint8 [n_pending, 160] and pending uint8 [n_pending, 112] as hs_initiate() wrote them
+        (pending is only read), ck_status int32 [n] (WG_HS_CK_*, by batch index), learned uint8 [n, 16]
+        (WG_HS_LEARNED_DTYPE), summary int32 [4] (n_ok, n_nopending, n_badauth, n_skipped). The opened cookies
+        go to the device's cookie table (hs_cookies_get)."""
+        np_ = pending.shape[0]
+        b = L.WgHsCookieOpenBatch(wire.data_ptr(), wire.numel(), pkt_off.data_ptr(), pkt_len.data_ptr(),
+                                  sent.data_ptr() if np_ else None, pending.data_ptr() if np_ else None,
+                                  ck_status.data_ptr(), learned.data_ptr(), summary.data_ptr(), pkt_off.shape[0], np_)
+        L.check(self._lib.wg_hs_cookie_open(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def hs_cookies_get(self, first_peer: int, n: int):
+        """wg_hs_cookies_get: (cookies, have) of peers [first_peer, first_peer + n): a list of 16-byte cookies and
+        a list of bools."""
+        ck = np.zeros(16 * n, np.uint8)
+        have = np.zeros(n, np.uint8)
+        L.check(self._lib.wg_hs_cookies_get(self.ctx, first_peer, n, ck.ctypes.data if n else None,
+                                            have.ctypes.data if n else None))
+        raw = ck.tobytes()
+        return [raw[16 * k:16 * k + 16] for k in range(n)], [bool(h) for h in have]
+
+    def hs_cookies_set(self, first_peer: int, cookies, have) -> None:
+        """wg_hs_cookies_set: the cookies of peers [first_peer, first_peer + n) (a sequence of 16-byte cookies, or
+        16 n bytes) and their `have` flags; have = False clears an entry (the host expires a cookie after 120 s)."""
+        if not isinstance(cookies, (bytes, bytearray, memoryview, np.ndarray)):
+            cookies = b"".join(bytes(x) for x in cookies)
+        ck = np.frombuffer(bytes(cookies), np.uint8).copy()
+        hv = np.array([1 if h else 0 for h in have], np.uint8)
+        if ck.size != 16 * hv.size:
+            raise L.WgError(L.WG_EINVAL, f"{ck.size} bytes of cookies for {hv.size} flags")
+        try:
+            L.check(self._lib.wg_hs_cookies_set(self.ctx, first_peer, hv.size, ck.ctypes.data if hv.size else None,
+                                                hv.ctypes.data if hv.size else None))
+        finally:
+            ck[:] = 0
+
+    def hs_mac2(self, records, peer, mac2_status, summary, stream: int | None = None) -> None:
+        """wg_hs_mac2 over torch tensors: records uint8 [n, 160] as hs_initiate() wrote them (the call writes mac2
+        into each record whose peer holds a cookie), peer int32 [n] (positions in the peer table), mac2_status
+        int32 [n] (WG_HS_MAC2_*), summary int32 [4] (n_ok, n_none, n_bad, 0)."""
+        b = L.WgHsMac2Batch(records.data_ptr(), peer.data_ptr(), mac2_status.data_ptr(), summary.data_ptr(),
+                            records.shape[0], 0)
+        L.check(self._lib.wg_hs_mac2(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
 
     def hs_stamp_host(self, init_entry, record, shared):
         """One wg_hs_init entry (a WG_HS_INIT_DTYPE scalar, as hs_open_host() returned it) with the record it came

@@ -279,3 +279,61 @@ def calculate_mac1(message_without_macs, public_key) -> bytes:
     static public key), for the outgoing side."""
     key = BLAKE2s256(b"mac1----", _bytes(public_key))
     return default_engine().blake2s_host([(_bytes(message_without_macs), key, 16)])[0]
+
+
+def HChaCha20(key, nonce16) -> bytes:
+    """HChaCha20 (draft-irtf-cfrg-xchacha-03 2.2): the 20 ChaCha rounds over {constants, key, nonce16} without the
+    final addition; state words 0-3 and 12-15. The rounds run on the device: a keystream block is the rounds' output
+    plus the input state, so the input words are taken off again."""
+    k, n = _bytes(key), _bytes(nonce16)
+    if len(k) != 32 or len(n) != 16:
+        raise ValueError("HChaCha20 takes a 32-byte key and a 16-byte nonce")
+    ks = struct.unpack("<16I", ChaCha20._cipher(k, n[4:], bytes(64), struct.unpack("<I", n[:4])[0]))
+    st = (0x61707865, 0x3320646E, 0x79622D32, 0x6B206574) + struct.unpack("<8I", k) + struct.unpack("<4I", n)
+    return struct.pack("<8I", *[(ks[j] - st[j]) & 0xFFFFFFFF for j in (0, 1, 2, 3, 12, 13, 14, 15)])
+
+
+class XChaCha20Poly1305:
+    """XChaCha20-Poly1305 (draft-irtf-cfrg-xchacha-03): HChaCha20, then ChaCha20Poly1305 under the subkey with the
+    nonce 0^4 || nonce24[16 .. 24). What a cookie reply is sealed with."""
+
+    @staticmethod
+    def _sub(key, nonce24):
+        n = _bytes(nonce24)
+        if len(n) != 24:
+            raise ValueError("an XChaCha20 nonce is 24 bytes")
+        return HChaCha20(key, n[:16]), bytes(4) + n[16:]
+
+    @staticmethod
+    def seal(key, nonce24, plaintext, aad=b"") -> bytes:
+        """ciphertext || tag"""
+        sub, n12 = XChaCha20Poly1305._sub(key, nonce24)
+        p = _bytes(plaintext)
+        ct, tag = bytearray(len(p)), bytearray(16)
+        ChaCha20Poly1305.poly1305AeadEncrypt(_bytes(aad), sub, n12, p, ct, tag)
+        return bytes(ct) + bytes(tag)
+
+    @staticmethod
+    def open(key, nonce24, sealed, aad=b"") -> bytes:
+        """the plaintext of ciphertext || tag; raises AEADBadTagException"""
+        sub, n12 = XChaCha20Poly1305._sub(key, nonce24)
+        c = _bytes(sealed)
+        if len(c) < 16:
+            raise AEADBadTagException("shorter than a tag")
+        pt = bytearray(len(c) - 16)
+        ChaCha20Poly1305.poly1305AeadDecrypt(_bytes(aad), sub, n12, c[:-16], pt, c[-16:])
+        return bytes(pt)
+
+
+def calculate_cookie(secret, addr, port: int) -> bytes:
+    """cookie(src) = BLAKE2s-128 keyed with the responder's secret over addr || port: addr is the 4 or 16 address
+    bytes, the port goes in network order."""
+    a = _bytes(addr)
+    if len(a) not in (4, 16):
+        raise ValueError("an address is 4 or 16 bytes")
+    return default_engine().blake2s_host([(a + struct.pack(">H", port), _bytes(secret), 16)])[0]
+
+
+def calculate_mac2(message_without_mac2, cookie) -> bytes:
+    """mac2 = BLAKE2s-128 keyed with the 16-byte cookie over the message up to its mac2 field."""
+    return default_engine().blake2s_host([(_bytes(message_without_mac2), _bytes(cookie), 16)])[0]
