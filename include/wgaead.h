@@ -1351,6 +1351,181 @@ int wg_rx_sessions_retire(wg_ctx* ctx, const uint32_t* indices_dev, uint32_t n, 
 int wg_rx_sessions_count(wg_ctx* ctx, uint32_t* live, uint32_t* retired);
 int wg_hs_install(wg_ctx* ctx, const wg_hs_install_batch* batch, void* stream);
 
+/* ---- session timers on the device ----
+ * The lifetime of the installed sessions: when a session stops being used (EstablishedSession.isExpired,
+ * EstablishedSession.java:28,:114), to whom the node initiates again (SessionManager.sessionInitiationThread,
+ * SessionManager.java:92-111; the retry after 5 s, :188) and when a keepalive is due (KeepaliveSender.java:29-85).
+ * The reference runs one thread per peer against the wall clock; here the host supplies a clock value and nothing
+ * per packet or per session, and a captured receive chain, transmit chain and tick replay with only `now` refreshed
+ * in place. A context that never calls wg_timers_* allocates nothing and behaves exactly as before.
+ *
+ * Time is a 64-bit tick count in a unit the host chooses, read on the device from `now` (device memory, 8-byte
+ * aligned) when a call runs. Tick 0 means "never": a call that reads *now == 0 changes no state, writes a zero
+ * summary (and, the sweep, an initiate list of padding only). An age is now >= t ? now - t : 0, so a clock that steps
+ * back ages nothing. The library has no clock of its own.
+ *
+ * State (wg_timers_reserve(ctx, max_peers); synchronous; it also creates the transmit state and reserves the
+ * sweep's scratch, so every call below can be captured; a second call with max_peers not above the first is a no-op,
+ * a larger one is WG_EINVAL: the state does not grow; max_peers above 2^30: WG_E2BIG):
+ *   per key slot a wg_timer_slot {state, peer, local_index, partner, born, last, last_data, superseded}. A session is
+ *     two records, the send slot's (state SEND_INITIATOR or SEND_RESPONDER) and the recv slot's (RECV), each naming
+ *     the other as `partner`. born: the tick of wg_timers_start. last: the last packet sent (send record) or
+ *     authenticated (recv record); last_data: the last one that was not a keepalive. superseded (send record): the
+ *     tick at which a newer session of the same peer became the peer's current one, 0: not superseded. It lives in
+ *     the session's own record because several superseded sessions of one peer can linger at once. DEAD: the session
+ *     was retired by the sweep or its other slot was taken by a newer session.
+ *   per peer (position in wg_hs_peers_set's table) a wg_timer_peer_state {current, flags, keepalive_interval,
+ *     rekey_listed}: current = the send slot of the session the peer transmits on (WG_TIMER_NOSLOT: none),
+ *     rekey_listed = the tick at which the sweep last listed the peer for initiation.
+ *   the configuration, a wg_timers_config at a fixed device address: a captured call sees a new configuration
+ *     without re-capture. Every field is a uint64, 0 = off: rekey_after_time, reject_after_time, rekey_timeout,
+ *     keepalive_timeout, linger, rekey_after_messages, reject_after_messages; flags: WG_TIMERS_INITIATOR_ONLY.
+ * wg_timers_config_set, wg_timers_peers_set (keepalive_interval and flags: WG_TIMER_PEER_CAN_INITIATE; a peer's
+ *   current and rekey_listed are kept), wg_timers_get and wg_timers_peers_get (host pointers) are synchronous and
+ *   ordered after everything queued on the device, like wg_tx_counters_get. Before wg_timers_reserve: WG_EINVAL; a
+ *   range past the key table / max_peers: WG_ERANGE. wg_ctx_destroy frees the state.
+ *
+ * The four calls are asynchronous on `stream` and capturable; each writes every output word it covers and nothing
+ * behind it, and depends on no thread order. They wait for, and are waited for by, each other on every stream.
+ *
+ * wg_timers_start(ctx, b, stream): after wg_hs_install on the same stream, with the install's own arrays. For every
+ *   j < min(*n_entries, n) with inst_status[j] == WG_HS_INST_OK (and, checked again, position < n_slots, both slots
+ *   inside the key table and different): the send slot's record = {SEND_INITIATOR for WG_HS_INSTALL_ESTABLISHED,
+ *   SEND_RESPONDER for WG_HS_INSTALL_SESSIONS; peer; local_index; partner = recv slot; born = now; 0; 0; superseded},
+ *   the recv slot's = {RECV, peer, local_index, partner = send slot, born = now, 0, 0, 0}. It reads position, peer
+ *   and local_index only, which WG_HS_INSTALL_WIPE leaves in place. A live session that owned either slot before
+ *   is killed first: its other record becomes DEAD, and the peer whose current it was has none. The session becomes
+ *   its peer's current and the previous current is superseded at `now`; of several OK entries of one peer in one
+ *   call the lowest j becomes current and the others start superseded at `now`. A peer at or past max_peers: the
+ *   records carry WG_HS_NOPEER; such a session can expire but is never rekeyed or kept alive. Three launches (the
+ *   peers' claim words = none; kill, and atomicMin of j on the peer's claim word; write), ordered by kernel
+ *   boundaries. n = 0 is a no-op.
+ *
+ * wg_timers_mark(ctx, b, stream): the per-packet part, over n descriptors and their statuses.
+ *   WG_TIMERS_RX, after wg_rx_deliver with its desc and final_status: WG_PKT_OK raises last and last_data of the
+ *     descriptor's key slot to now, WG_PKT_KEEPALIVE raises last only; only a RECV record is marked.
+ *   WG_TIMERS_TX, between wg_tx_plan and wg_seal_batch with desc_out and tx_status: a WG_PKT_OK descriptor raises
+ *     last of its key slot, and last_data if len > 0; only a live SEND record is marked. With WG_TIMERS_GATE a
+ *     WG_PKT_OK descriptor whose slot lies in [slot_first, slot_first + slot_count) is refused when the slot holds
+ *     no live SEND record (a slot past the key table holds none), or reject_after_time is set and the session's age
+ *     has reached it, or reject_after_messages is set and desc.counter has reached it: status = WG_PKT_NOSESSION,
+ *     len = WG_LEN_INVALID, so the seal and the framer skip it, and nothing is marked. Its claimed counter is lost,
+ *     which is harmless. Transmission on an old session thus stops at the packet, not at the next tick.
+ *   A raise is a 64-bit atomic maximum: marks on streams with different clocks cannot move a stamp back. Slots
+ *   outside the key table, records of any other state and every other status are ignored. summary = {n_marked,
+ *   n_refused}. desc and status are in and out in TX direction with the gate, inputs otherwise. n = 0 writes a
+ *   zero summary.
+ *
+ * wg_timers_sweep(ctx, b, stream): the tick, over every slot record and every peer record. Three lists, each with a
+ *   capacity; what does not fit is neither listed nor changed and stays due. A session (a live SEND record) is
+ *   EXPIRED when reject_after_time is set and its age has reached it, or reject_after_messages is set and its send
+ *   counter has reached it, or linger is set and it was superseded linger or more ticks ago.
+ *   expired[0 .. n_expired): the expired sessions in ascending send-slot order, {send_slot, recv_slot, peer,
+ *     local_index}. With WG_TIMERS_RETIRE each listed session's local_index is retired in the receiver-index table
+ *     (the compare-and-swap of wg_rx_sessions_retire), both records become DEAD, and the peer whose current it was
+ *     has none. Without the flag it is listed at every sweep. An expired session is listed for nothing else.
+ *   initiate[0 .. n_initiate): in ascending order the peers that have WG_TIMER_PEER_CAN_INITIATE, and no current
+ *     session or an expired one (whether or not this sweep's list had room to retire it), or one whose age has
+ *     reached rekey_after_time or whose send counter has reached rekey_after_messages and, under
+ *     WG_TIMERS_INITIATOR_ONLY, that we initiated; and rekey_listed == 0 or now - rekey_listed >= rekey_timeout.
+ *     rekey_listed = now for a listed peer. initiate[n_initiate .. initiate_cap) = 0xFFFFFFFF, so a captured
+ *     wg_hs_initiate over the whole capacity answers them WG_HS_INIT_BADPEER and consumes no ephemeral.
+ *   keepalives[0 .. n_keepalive): in ascending send-slot order, for sessions that are their peer's current and not
+ *     expired. Persistent: the peer's keepalive_interval > 0 and the send record's last == 0 (KeepaliveSender.java:
+ *     69-73 sends one as soon as the session changes) or now - last >= interval. Passive: keepalive_timeout > 0, the
+ *     recv record's last_data > the send record's last (equal ticks count as answered) and now - last_data >=
+ *     keepalive_timeout. Entry j = {in_off = 0, out_off = wire_base + j * wire_stride + 16, counter = send[slot], len
+ *     = 0, key_slot = slot}; then send[slot] += 1 and last = now. wg_seal_batch(keepalives, n_keepalive, ...,
+ *     WG_F_FRAME) sends them, in route mode too. Wire slots that overrun out_size (counted as wg_tx_plan counts
+ *     them; wire_stride < 32: none fits) lower the capacity. keepalives[n_keepalive .. keepalive_cap) = {0, 0, 0,
+ *     WG_LEN_INVALID, 0}, which the seal and the framer skip: a captured seal over the whole capacity sends exactly
+ *     the listed ones, so a tick -> seal chain replays with no read-back either.
+ *   summary = {n_expired_due, n_expired, n_initiate_due, n_initiate, n_keepalive_due, n_keepalive, n_live (sessions
+ *   alive after the sweep), 0}. The call waits for, and is waited for by, the transmit plans, and with
+ *   WG_TIMERS_RETIRE the receive plans, of every stream. Three launches: every record's verdict and one 16-byte
+ *   record {expired, live, initiate, keepalive} per 256 positions (position i is key slot i and peer i; a peer's
+ *   verdict tests its current session's expiry itself, so it waits for no slot's), their prefixes, the placing. */
+#define WG_TIMER_NONE 0u
+#define WG_TIMER_SEND_INITIATOR 1u
+#define WG_TIMER_SEND_RESPONDER 2u
+#define WG_TIMER_RECV 3u
+#define WG_TIMER_DEAD 4u
+#define WG_TIMER_NOSLOT 0xFFFFFFFFu
+#define WG_TIMERS_INITIATOR_ONLY 1u   /* wg_timers_config.flags */
+#define WG_TIMER_PEER_CAN_INITIATE 1u /* wg_timer_peer.flags */
+#define WG_TIMERS_RX 0u               /* wg_timers_mark_batch.dir */
+#define WG_TIMERS_TX 1u
+#define WG_TIMERS_GATE 1u             /* wg_timers_mark_batch.flags */
+#define WG_TIMERS_RETIRE 1u           /* wg_timers_sweep_batch.flags */
+typedef struct wg_timers_config { /* 64 bytes; 0 = off */
+  uint64_t rekey_after_time, reject_after_time, rekey_timeout, keepalive_timeout, linger;
+  uint64_t rekey_after_messages, reject_after_messages;
+  uint64_t flags; /* WG_TIMERS_INITIATOR_ONLY */
+} wg_timers_config;
+typedef struct wg_timer_slot { /* 48 bytes */
+  uint32_t state, peer, local_index, partner;
+  uint64_t born, last, last_data, superseded;
+} wg_timer_slot;
+typedef struct wg_timer_peer { /* 16 bytes */
+  uint64_t keepalive_interval;
+  uint32_t flags; /* WG_TIMER_PEER_CAN_INITIATE */
+  uint32_t _zero;
+} wg_timer_peer;
+typedef struct wg_timer_peer_state { /* 24 bytes */
+  uint32_t current; /* send slot, or WG_TIMER_NOSLOT */
+  uint32_t flags;
+  uint64_t keepalive_interval, rekey_listed;
+} wg_timer_peer_state;
+typedef struct wg_timer_expired { /* 16 bytes */
+  uint32_t send_slot, recv_slot, peer, local_index;
+} wg_timer_expired;
+typedef struct wg_timers_start_batch {
+  const void* entries;         /* device: the install's entries */
+  const uint32_t* n_entries;   /* device, or NULL: all n */
+  const uint32_t* inst_status; /* device, n entries: the install's */
+  const uint32_t* send_slot;   /* device, n_slots entries */
+  const uint32_t* recv_slot;   /* device, n_slots entries */
+  const uint64_t* now;         /* device, 8-byte aligned */
+  uint32_t n, n_slots;
+  uint32_t source;             /* WG_HS_INSTALL_SESSIONS or WG_HS_INSTALL_ESTABLISHED */
+  uint32_t _reserved;
+} wg_timers_start_batch;
+typedef struct wg_timers_mark_summary {
+  uint32_t n_marked, n_refused;
+} wg_timers_mark_summary;
+typedef struct wg_timers_mark_batch {
+  wg_pkt* desc;                    /* device, 16-byte aligned, n entries; in and out with WG_TIMERS_GATE */
+  uint32_t* status;                /* device, n entries: final_status / tx_status; in and out with WG_TIMERS_GATE */
+  const uint64_t* now;             /* device, 8-byte aligned */
+  wg_timers_mark_summary* summary; /* device, 8 bytes, 8-byte aligned */
+  uint32_t n;
+  uint32_t dir;                    /* WG_TIMERS_RX or WG_TIMERS_TX */
+  uint32_t flags;                  /* WG_TIMERS_GATE (TX only) */
+  uint32_t slot_first, slot_count; /* the gated key slots */
+  uint32_t _reserved;
+} wg_timers_mark_batch;
+typedef struct wg_timers_sweep_summary {
+  uint32_t n_expired_due, n_expired, n_initiate_due, n_initiate, n_keepalive_due, n_keepalive, n_live, _zero;
+} wg_timers_sweep_summary;
+typedef struct wg_timers_sweep_batch {
+  const uint64_t* now;              /* device, 8-byte aligned */
+  wg_timer_expired* expired;        /* device, 16-byte aligned, expired_cap entries */
+  uint32_t* initiate;               /* device, initiate_cap entries: wg_hs_initiate_batch.peer */
+  wg_pkt* keepalives;               /* device, 16-byte aligned, keepalive_cap entries */
+  wg_timers_sweep_summary* summary; /* device, 32 bytes, 8-byte aligned */
+  uint64_t wire_base, wire_stride, out_size; /* the keepalives' wire slots, as in wg_tx_batch */
+  uint32_t expired_cap, initiate_cap, keepalive_cap;
+  uint32_t flags;                   /* WG_TIMERS_RETIRE */
+} wg_timers_sweep_batch;
+int wg_timers_reserve(wg_ctx* ctx, uint32_t max_peers);
+int wg_timers_config_set(wg_ctx* ctx, const wg_timers_config* config);
+int wg_timers_peers_set(wg_ctx* ctx, uint32_t first_peer, uint32_t n, const wg_timer_peer* peers_host);
+int wg_timers_get(wg_ctx* ctx, uint32_t first_slot, uint32_t n, wg_timer_slot* out_host);
+int wg_timers_peers_get(wg_ctx* ctx, uint32_t first_peer, uint32_t n, wg_timer_peer_state* out_host);
+int wg_timers_start(wg_ctx* ctx, const wg_timers_start_batch* batch, void* stream);
+int wg_timers_mark(wg_ctx* ctx, const wg_timers_mark_batch* batch, void* stream);
+int wg_timers_sweep(wg_ctx* ctx, const wg_timers_sweep_batch* batch, void* stream);
+
 int wg_seal1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* pt, uint32_t len, uint8_t* out);
 int wg_open1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* in, uint32_t len, uint8_t* pt);
 int wg_pp_config(wg_ctx* ctx, uint32_t waves, uint32_t idle_us);

@@ -16,4 +16,5 @@ from .engine import Engine, default_engine, desc_as_int64, pack_desc, selftest, 
 from .engine import pack_b2s_desc, WG_B2S_DTYPE, WG_HS_RECORD_DTYPE  # noqa: F401
 from .engine import pack_x25519_desc, WG_X25519_DTYPE, WG_HS_INIT_DTYPE, WG_HS_SESSION_DTYPE  # noqa: F401
 from .engine import WG_HS_PENDING_DTYPE, WG_HS_ESTABLISHED_DTYPE  # noqa: F401
+from .engine import TimersConfig, WG_TIMER_SLOT_DTYPE, WG_TIMER_PEER_STATE_DTYPE, WG_TIMER_EXPIRED_DTYPE  # noqa: F401
 from .engine import WG_HS_SRC_DTYPE, WG_HS_COOKIE_REPLY_DTYPE, WG_HS_LEARNED_DTYPE  # noqa: F401

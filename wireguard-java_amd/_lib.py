@@ -95,6 +95,13 @@ WG_HS_INST_FULL = 4
 WG_HS_INSTALL_SESSIONS = 0
 WG_HS_INSTALL_ESTABLISHED = 1
 WG_HS_INSTALL_WIPE = 1
+WG_TIMER_NONE, WG_TIMER_SEND_INITIATOR, WG_TIMER_SEND_RESPONDER, WG_TIMER_RECV, WG_TIMER_DEAD = 0, 1, 2, 3, 4
+WG_TIMER_NOSLOT = 0xFFFFFFFF
+WG_TIMERS_INITIATOR_ONLY = 1
+WG_TIMER_PEER_CAN_INITIATE = 1
+WG_TIMERS_RX, WG_TIMERS_TX = 0, 1
+WG_TIMERS_GATE = 1
+WG_TIMERS_RETIRE = 1
 WG_HS_TS_OK = 0
 WG_HS_TS_REPLAY = 1
 WG_HS_TS_SUPERSEDED = 2
@@ -384,6 +391,56 @@ class WgHsInstallBatch(ctypes.Structure):
                 ("flags", ctypes.c_uint32)]
 
 
+class WgTimersConfig(ctypes.Structure):
+    """wg_timers_config: the session timers' limits in ticks and messages (0 = off)."""
+    _fields_ = [("rekey_after_time", ctypes.c_uint64), ("reject_after_time", ctypes.c_uint64),
+                ("rekey_timeout", ctypes.c_uint64), ("keepalive_timeout", ctypes.c_uint64), ("linger", ctypes.c_uint64),
+                ("rekey_after_messages", ctypes.c_uint64), ("reject_after_messages", ctypes.c_uint64),
+                ("flags", ctypes.c_uint64)]
+
+
+class WgTimerSlot(ctypes.Structure):
+    """wg_timer_slot: one key slot's timer record."""
+    _fields_ = [("state", ctypes.c_uint32), ("peer", ctypes.c_uint32), ("local_index", ctypes.c_uint32),
+                ("partner", ctypes.c_uint32), ("born", ctypes.c_uint64), ("last", ctypes.c_uint64),
+                ("last_data", ctypes.c_uint64), ("superseded", ctypes.c_uint64)]
+
+
+class WgTimerPeer(ctypes.Structure):
+    """wg_timer_peer: what wg_timers_peers_set sets per peer."""
+    _fields_ = [("keepalive_interval", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("_zero", ctypes.c_uint32)]
+
+
+class WgTimerPeerState(ctypes.Structure):
+    """wg_timer_peer_state: one peer's timer record."""
+    _fields_ = [("current", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("keepalive_interval", ctypes.c_uint64),
+                ("rekey_listed", ctypes.c_uint64)]
+
+
+class WgTimersStartBatch(ctypes.Structure):
+    """wg_timers_start_batch: one wg_timers_start call (device pointers)."""
+    _fields_ = [("entries", ctypes.c_void_p), ("n_entries", ctypes.c_void_p), ("inst_status", ctypes.c_void_p),
+                ("send_slot", ctypes.c_void_p), ("recv_slot", ctypes.c_void_p), ("now", ctypes.c_void_p),
+                ("n", ctypes.c_uint32), ("n_slots", ctypes.c_uint32), ("source", ctypes.c_uint32),
+                ("_reserved", ctypes.c_uint32)]
+
+
+class WgTimersMarkBatch(ctypes.Structure):
+    """wg_timers_mark_batch: one wg_timers_mark call (device pointers)."""
+    _fields_ = [("desc", ctypes.c_void_p), ("status", ctypes.c_void_p), ("now", ctypes.c_void_p),
+                ("summary", ctypes.c_void_p), ("n", ctypes.c_uint32), ("dir", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("slot_first", ctypes.c_uint32), ("slot_count", ctypes.c_uint32),
+                ("_reserved", ctypes.c_uint32)]
+
+
+class WgTimersSweepBatch(ctypes.Structure):
+    """wg_timers_sweep_batch: one wg_timers_sweep call (device pointers)."""
+    _fields_ = [("now", ctypes.c_void_p), ("expired", ctypes.c_void_p), ("initiate", ctypes.c_void_p),
+                ("keepalives", ctypes.c_void_p), ("summary", ctypes.c_void_p), ("wire_base", ctypes.c_uint64),
+                ("wire_stride", ctypes.c_uint64), ("out_size", ctypes.c_uint64), ("expired_cap", ctypes.c_uint32),
+                ("initiate_cap", ctypes.c_uint32), ("keepalive_cap", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
 class WgCompletion(ctypes.Structure):
     """wg_completion: one reaped packet of a wg_queue."""
     _fields_ = [("user", ctypes.c_uint64), ("counter", ctypes.c_uint64), ("data", ctypes.c_void_p),
@@ -407,6 +464,9 @@ assert ctypes.sizeof(WgX25519Desc) == 32 and ctypes.sizeof(WgHsDhBatch) == 40
 assert ctypes.sizeof(WgHsInit) == 144 and ctypes.sizeof(WgHsOpenSummary) == 16 and ctypes.sizeof(WgHsOpenBatch) == 64
 assert ctypes.sizeof(WgHsSession) == 176 and ctypes.sizeof(WgHsRespondSummary) == 16 and ctypes.sizeof(WgHsRespondBatch) == 64
 assert ctypes.sizeof(WgHsInstallSummary) == 16 and ctypes.sizeof(WgHsInstallBatch) == 80
+assert ctypes.sizeof(WgTimersConfig) == 64 and ctypes.sizeof(WgTimerSlot) == 48 and ctypes.sizeof(WgTimerPeer) == 16
+assert ctypes.sizeof(WgTimerPeerState) == 24 and ctypes.sizeof(WgTimersStartBatch) == 64
+assert ctypes.sizeof(WgTimersMarkBatch) == 56 and ctypes.sizeof(WgTimersSweepBatch) == 80
 assert ctypes.sizeof(WgHsStampSummary) == 16 and ctypes.sizeof(WgHsStampBatch) == 80
 assert ctypes.sizeof(WgHsSrc) == 24 and ctypes.sizeof(WgHsCookieReply) == 80 and ctypes.sizeof(WgHsAdmitSummary) == 16
 assert ctypes.sizeof(WgHsAdmitBatch) == 112 and ctypes.sizeof(WgHsLearned) == 16 and ctypes.sizeof(WgHsCookieOpenSummary) == 16
@@ -478,6 +538,14 @@ SIGNATURES = [
     ("wg_rx_sessions_retire", _I, [_VP, _VP, _U32, _VP, _VP]),
     ("wg_rx_sessions_count", _I, [_VP, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
     ("wg_hs_install", _I, [_VP, ctypes.POINTER(WgHsInstallBatch), _VP]),
+    ("wg_timers_reserve", _I, [_VP, _U32]),
+    ("wg_timers_config_set", _I, [_VP, ctypes.POINTER(WgTimersConfig)]),
+    ("wg_timers_peers_set", _I, [_VP, _U32, _U32, _VP]),
+    ("wg_timers_get", _I, [_VP, _U32, _U32, _VP]),
+    ("wg_timers_peers_get", _I, [_VP, _U32, _U32, _VP]),
+    ("wg_timers_start", _I, [_VP, ctypes.POINTER(WgTimersStartBatch), _VP]),
+    ("wg_timers_mark", _I, [_VP, ctypes.POINTER(WgTimersMarkBatch), _VP]),
+    ("wg_timers_sweep", _I, [_VP, ctypes.POINTER(WgTimersSweepBatch), _VP]),
     ("wg_seal1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_open1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_pp_config", _I, [_VP, _U32, _U32]),

@@ -53,6 +53,44 @@ WG_HS_ESTABLISHED_DTYPE = np.dtype([("index", "<u4"), ("record", "<u4"), ("pendi
 WG_HS_SRC_DTYPE = np.dtype([("addr", "u1", (16,)), ("port", "u1", (2,)), ("family", "u1"), ("_pad", "u1", (5,))])
 WG_HS_COOKIE_REPLY_DTYPE = np.dtype([("index", "<u4"), ("len", "<u4"), ("msg", "u1", (64,)), ("_pad", "<u4", (2,))])
 WG_HS_LEARNED_DTYPE = np.dtype([("index", "<u4"), ("pending", "<u4"), ("peer", "<u4"), ("_zero", "<u4")])
+WG_TIMER_SLOT_DTYPE = np.dtype([("state", "<u4"), ("peer", "<u4"), ("local_index", "<u4"), ("partner", "<u4"),
+                                ("born", "<u8"), ("last", "<u8"), ("last_data", "<u8"), ("superseded", "<u8")])
+WG_TIMER_PEER_DTYPE = np.dtype([("keepalive_interval", "<u8"), ("flags", "<u4"), ("_zero", "<u4")])
+WG_TIMER_PEER_STATE_DTYPE = np.dtype([("current", "<u4"), ("flags", "<u4"), ("keepalive_interval", "<u8"),
+                                      ("rekey_listed", "<u8")])
+WG_TIMER_EXPIRED_DTYPE = np.dtype([("send_slot", "<u4"), ("recv_slot", "<u4"), ("peer", "<u4"), ("local_index", "<u4")])
+
+
+class TimersConfig:
+    """wg_timers_config: the session timers' limits, times in ticks, 0 = off."""
+    FIELDS = ("rekey_after_time", "reject_after_time", "rekey_timeout", "keepalive_timeout", "linger",
+              "rekey_after_messages", "reject_after_messages", "flags")
+
+    def __init__(self, **kw):
+        for f in self.FIELDS:
+            setattr(self, f, int(kw.pop(f, 0)))
+        if kw:
+            raise TypeError(f"unknown timers fields {sorted(kw)}")
+
+    @classmethod
+    def reference(cls, ticks_per_s: int) -> "TimersConfig":
+        """The reference's rules: a session expires 120 s after its creation (EstablishedSession.java:28,:114), which
+        only makes the node initiate again (SessionManager.java:92-111), and a failed attempt is retried after 5 s
+        (SessionManager.java:188). It never stops using a session: everything else is off."""
+        return cls(rekey_after_time=120 * ticks_per_s, rekey_timeout=5 * ticks_per_s)
+
+    @classmethod
+    def wireguard(cls, ticks_per_s: int) -> "TimersConfig":
+        """WireGuard's constants: REKEY_AFTER_TIME 120 s, REJECT_AFTER_TIME 180 s, REKEY_TIMEOUT 5 s, KEEPALIVE_TIMEOUT
+        10 s, a superseded session lingers for 180 s, REKEY_AFTER_MESSAGES 2^60, REJECT_AFTER_MESSAGES 2^64 - 2^13 - 1;
+        only the initiator of a session rekeys it."""
+        t = ticks_per_s
+        return cls(rekey_after_time=120 * t, reject_after_time=180 * t, rekey_timeout=5 * t, keepalive_timeout=10 * t,
+                   linger=180 * t, rekey_after_messages=1 << 60, reject_after_messages=(1 << 64) - (1 << 13) - 1,
+                   flags=L.WG_TIMERS_INITIATOR_ONLY)
+
+    def as_struct(self) -> "L.WgTimersConfig":
+        return L.WgTimersConfig(*(getattr(self, f) for f in self.FIELDS))
 
 
 def pack_b2s_desc(in_off, out_off, key_off, length, outlen, keylen) -> np.ndarray:
@@ -366,6 +404,81 @@ class Engine:
                                summary.data_ptr(), entries.shape[0], send_slot.shape[0], slot_first, slot_count, source,
                                L.WG_HS_INSTALL_WIPE if wipe else 0)
         L.check(self._lib.wg_hs_install(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    # ---- session timers (wg_timers_*) --------------------------------------------------------
+    def timers_reserve(self, max_peers: int) -> None:
+        """wg_timers_reserve: the timer records of every key slot and of max_peers peers, the transmit state and the
+        sweep's scratch. Needed before every other timers_* call."""
+        L.check(self._lib.wg_timers_reserve(self.ctx, max_peers))
+
+    def timers_config_set(self, config: "TimersConfig") -> None:
+        """wg_timers_config_set: a TimersConfig; captured calls see it without re-capture."""
+        c = config.as_struct()
+        L.check(self._lib.wg_timers_config_set(self.ctx, ctypes.byref(c)))
+
+    def timers_peers_set(self, first_peer: int, peers) -> None:
+        """wg_timers_peers_set: peers = [(keepalive_interval, can_initiate), ...] from first_peer on."""
+        v = np.zeros(len(peers), WG_TIMER_PEER_DTYPE)
+        for k, (interval, can) in enumerate(peers):
+            v[k] = (interval, L.WG_TIMER_PEER_CAN_INITIATE if can else 0, 0)
+        L.check(self._lib.wg_timers_peers_set(self.ctx, first_peer, len(v), v.ctypes.data if len(v) else None))
+
+    def timers_get(self, first_slot: int, n: int) -> np.ndarray:
+        """wg_timers_get: the timer records of key slots [first_slot, first_slot + n), after everything queued
+        (WG_TIMER_SLOT_DTYPE array)."""
+        v = np.zeros(max(n, 1), WG_TIMER_SLOT_DTYPE)
+        L.check(self._lib.wg_timers_get(self.ctx, first_slot, n, v.ctypes.data))
+        return v[:n]
+
+    def timers_peers_get(self, first_peer: int, n: int) -> np.ndarray:
+        """wg_timers_peers_get: the peers' timer records (WG_TIMER_PEER_STATE_DTYPE array)."""
+        v = np.zeros(max(n, 1), WG_TIMER_PEER_STATE_DTYPE)
+        L.check(self._lib.wg_timers_peers_get(self.ctx, first_peer, n, v.ctypes.data))
+        return v[:n]
+
+    def timers_start(self, entries, summary_n, inst_status, send_slot, recv_slot, now, source: int,
+                     stream: int | None = None) -> None:
+        """wg_timers_start over the tensors hs_install() was given, behind it on the same stream; now int64 [1]."""
+        b = L.WgTimersStartBatch(entries.data_ptr(), summary_n.data_ptr() if summary_n is not None else None,
+                                 inst_status.data_ptr(), send_slot.data_ptr() if send_slot.shape[0] else None,
+                                 recv_slot.data_ptr() if recv_slot.shape[0] else None, now.data_ptr(), entries.shape[0],
+                                 send_slot.shape[0], source, 0)
+        L.check(self._lib.wg_timers_start(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def timers_mark(self, desc, status, now, summary, tx: bool = False, gate: bool = False, slot_first: int = 0,
+                    slot_count: int = 0, stream: int | None = None) -> None:
+        """wg_timers_mark over torch tensors: desc int64 [n, 4] and status int32 [n] as rx_deliver() (final_status) or
+        tx_plan() left them, now int64 [1], summary int32 [2] (n_marked, n_refused). tx=True with gate=True refuses
+        descriptors on dead or worn-out sessions of key slots [slot_first, slot_first + slot_count) before the seal."""
+        n = desc.shape[0]
+        b = L.WgTimersMarkBatch(desc.data_ptr() if n else None, status.data_ptr() if n else None, now.data_ptr(),
+                                summary.data_ptr(), n, L.WG_TIMERS_TX if tx else L.WG_TIMERS_RX,
+                                L.WG_TIMERS_GATE if gate else 0, slot_first, slot_count, 0)
+        L.check(self._lib.wg_timers_mark(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def timers_sweep(self, now, expired, initiate, keepalives, summary, wire_stride: int = 0, out_size: int = 0,
+                     wire_base: int = 0, retire: bool = False, stream: int | None = None) -> None:
+        """wg_timers_sweep over torch tensors: expired int32 [cap, 4] (send slot, recv slot, peer, local index),
+        initiate int32 [cap] (hs_initiate()'s peer array, padded with -1), keepalives int64 [cap, 4] (wg_pkt records for
+        seal(frame=True) into wire slots of wire_stride bytes of a ring of out_size bytes), summary int32 [8]
+        (expired due / listed, initiate due / listed, keepalives due / listed, live sessions, 0)."""
+        b = L.WgTimersSweepBatch(now.data_ptr(), expired.data_ptr() if expired.shape[0] else None,
+                                 initiate.data_ptr() if initiate.shape[0] else None,
+                                 keepalives.data_ptr() if keepalives.shape[0] else None, summary.data_ptr(), wire_base,
+                                 wire_stride, out_size, expired.shape[0], initiate.shape[0], keepalives.shape[0],
+                                 L.WG_TIMERS_RETIRE if retire else 0)
+        L.check(self._lib.wg_timers_sweep(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def timers_tick(self, now, expired, initiate, keepalives, summary, out, wire_stride: int, wire_base: int = 0,
+                    retire: bool = True, stream: int | None = None) -> None:
+        """The tick on one stream, next to rx_open and tx_seal: timers_sweep, then the keepalives it listed are sealed
+        and framed into `out` (the sweep pads the list with descriptors the seal skips: nothing is read back). The receiver table
+        (set_receivers) must be set."""
+        st = stream if stream is not None else _torch_stream()
+        self.timers_sweep(now, expired, initiate, keepalives, summary, wire_stride=wire_stride, out_size=out.numel(),
+                          wire_base=wire_base, retire=retire, stream=st)
+        if keepalives.shape[0]:
+            self.seal(keepalives, out, out, 16, stream=st, frame=True)
 
     def rx_plan(self, wire, pkt_off, pkt_len, desc_out, rx_status, host_list, summary, max_len: int,
                 packed: bool = False, pt_base: int = 0, pt_size: int = 0, stream: int | None = None) -> None:
