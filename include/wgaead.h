@@ -1526,6 +1526,168 @@ int wg_timers_start(wg_ctx* ctx, const wg_timers_start_batch* batch, void* strea
 int wg_timers_mark(wg_ctx* ctx, const wg_timers_mark_batch* batch, void* stream);
 int wg_timers_sweep(wg_ctx* ctx, const wg_timers_sweep_batch* batch, void* stream);
 
+/* ---- endpoints on the device: learn, roam, and the send lists ----
+ * Where a sealed datagram goes. The reference gives every session one address, EstablishedSession.
+ * outboundPacketAddress: a responder's session gets the initiation's origin (SessionManager.java:217-229), an
+ * initiator's the configured endpoint (:186, :196), and nothing moves it. WireGuard additionally moves a peer's
+ * endpoint to the source of every authenticated packet (roaming). Both rules are here, per call, and the transmit side
+ * gets what wg_rx_deliver's items are for the receive side: a list the host walks with sendmmsg, so neither tx_status
+ * nor a descriptor is read back and the host keeps no slot -> peer -> address table. Configuration (Endpoint =), DNS
+ * and the sockets stay on the host. A context that never calls wg_endpoints_* allocates nothing and behaves exactly as
+ * before.
+ *
+ * State (wg_endpoints_reserve(ctx, max_peers); synchronous; a second call with max_peers not above the first is a
+ * no-op, a larger one is WG_EINVAL: the state does not grow; max_peers above 2^30: WG_E2BIG), all of it at device
+ * addresses that are fixed for the life of the context, so a setter needs no re-capture:
+ *   per peer (position in wg_hs_peers_set's table) one 24-byte wg_hs_src, the endpoint; family 0: none (24 zero bytes,
+ *     the state at creation). The stored form is normalised: family 4 keeps addr[4 .. 16) zero, and _pad is zero, so
+ *     two endpoints are equal exactly when their 24 bytes are.
+ *   per key slot the peer it belongs to (uint32; WG_HS_NOPEER at creation).
+ *   scratch: one claim word per peer, and the send lists' ranks for 2^22 descriptors per call; a larger call grows
+ *     them, except on a capturing stream (WG_EINVAL: run one call of that size outside the capture first).
+ * wg_endpoints_set / wg_endpoints_get(ctx, first_peer, n, wg_hs_src*) and wg_endpoint_slots_set / wg_endpoint_slots_get
+ *   (ctx, first_slot, n, uint32_t* peers; for sessions keyed with wg_keys_set) take host pointers, are synchronous and
+ *   ordered after everything queued on the device, like wg_tx_counters_set. The setter stores the normalised form; a
+ *   family outside {0, 4, 6}: WG_EINVAL with nothing changed. A range past max_peers / the key table: WG_ERANGE.
+ *   Every call of this section before wg_endpoints_reserve: WG_EINVAL. wg_keys_set / wg_keys_zero do NOT touch the
+ *   map: a host that re-keys a slot by hand sets the slot's peer by hand. wg_ctx_destroy frees the state.
+ *
+ * The four calls below are asynchronous on `stream` and capturable after the reserve; each writes every output word it
+ * covers and nothing behind it, writes every scratch word before it reads it, depends on no thread order, and waits
+ * for, and is waited for by, the others on every stream. n above 2^30: WG_E2BIG. Summaries are 8-byte aligned, src
+ * arrays 8, items and descriptors and entries 16, everything else 4; a misaligned pointer, or an output that overlaps
+ * another output or an input, is WG_EINVAL.
+ *
+ * wg_endpoints_start(ctx, b, stream): after wg_hs_install on the same stream, with the install's own arrays, as
+ *   wg_timers_start; src / n_src is the ring's wg_hs_src array by batch index. For every j < min(*n_entries, n) with
+ *   inst_status[j] == WG_HS_INST_OK (and, checked again, position < n_slots, both slots inside the key table and
+ *   different): the map entries of both slots become the entry's peer, WG_HS_NOPEER for a peer at or past max_peers
+ *   (n_nopeer counts those sessions). The endpoint: with WG_HS_INSTALL_SESSIONS, endpoint[peer] = the normalised
+ *   src[entry.index], the reference's initiation.originAddress(); with WG_HS_INSTALL_ESTABLISHED it is unchanged (the
+ *   reference keeps connectionInfo.endpoint()) unless WG_EP_LEARN_RESPONSE is set (WireGuard: the response's source).
+ *   An entry whose index >= n_src, or whose src.family is neither 4 nor 6, leaves the endpoint alone and is counted in
+ *   n_badsrc. Of several OK entries of one peer in one call the lowest j, the entry wg_timers_start makes current,
+ *   gives the endpoint (if its source is unusable, none does). summary = {n_sessions, n_learned (endpoints written),
+ *   n_badsrc, n_nopeer}; n_learned and n_badsrc are 0 where nothing is learned. Up to three launches (the peers' claim
+ *   words = none; the map, and atomicMin of j on the peer's claim word; the endpoints). n = 0 writes a zero summary.
+ *
+ * wg_endpoints_learn(ctx, b, stream): roaming, after wg_rx_deliver with its desc and final_status; src by batch index.
+ *   Packet i qualifies if final_status[i] is WG_PKT_OK or WG_PKT_KEEPALIVE (authenticated and past the replay check),
+ *   desc[i].key_slot is inside the key table, the slot's peer p < max_peers, and src[i].family is 4 or 6 (a packet
+ *   that fails only the last test is counted in n_badsrc). For each peer with qualifying packets the one with the
+ *   highest batch index wins, the last to arrive, whatever the dispatch order (an atomicMax per peer, read one launch
+ *   later; a wave whose qualifying lanes all name one peer issues one atomic). If the normalised winner differs from
+ *   endpoint[p] it replaces it and p has roamed. roamed[0 .. min(n_roamed, roamed_cap)) = the roamed peers in
+ *   ascending order; a peer that does not fit is still updated. summary = {n_authentic (qualifying packets), n_peers
+ *   (peers with one), n_roamed, n_badsrc}. Five launches (claim words = 0; claim; judge and update, one thread per
+ *   peer; prefixes; place). n = 0 writes a zero summary. The reference never roams: a node that wants its behaviour
+ *   does not call this.
+ *
+ * wg_tx_sendlist(ctx, b, stream): over n descriptors and, optionally, their statuses: wg_tx_plan's desc_out /
+ *   tx_status (after an optional wg_timers_mark gate), or wg_timers_sweep's keepalives with status = NULL. Descriptor
+ *   j is LIVE if len != WG_LEN_INVALID and, when status is given, status[j] == WG_PKT_OK. A live descriptor is LISTED
+ *   if its key slot is inside the key table, the slot's peer p < max_peers and endpoint[p].family != 0. items[0 ..
+ *   n_items) is the stable compaction of the listed descriptors in j order, as 48-byte wg_tx_item {off = out_off - 16
+ *   (the wire packet's start in the seal's output buffer), len = desc.len + 32 (header, ciphertext, tag), key_slot,
+ *   peer, index = j, dst = endpoint[p]}. A live descriptor that is not listed is counted in n_noendpoint. With
+ *   WG_SEND_GATE, valid only BEFORE the seal on the same stream, such a descriptor is refused as the timers' gate
+ *   refuses: status[j] = WG_PKT_NOENDPOINT (when status is given), len = WG_LEN_INVALID, so the seal and the framer
+ *   skip it; its claimed counter is lost, which is harmless. summary = {bytes (the sum of the items' len), n_items,
+ *   n_noendpoint}. desc and status are in and out with the gate, inputs otherwise. Three launches (judge, prefixes,
+ *   place). n = 0 writes a zero summary.
+ *
+ * wg_hs_sendlist(ctx, b, stream): the same items for the handshake messages, which lie in struct arrays: off is
+ *   relative to the start of `entries`, key_slot = 0xFFFFFFFF, index = the entry's position k. By kind:
+ *   WG_HS_SEND_RESPONSES: entries = wg_hs_respond's sessions, n_entries = &wg_hs_respond_summary.n_ok; off = 176 k +
+ *     16, len = 92, peer = sessions[k].peer, dst = the normalised src[sessions[k].index].
+ *   WG_HS_SEND_INITIATIONS: entries = wg_hs_initiate's records with its status and peer arrays; only WG_HS_INIT_OK
+ *     entries; off = 160 k + 8, len = records[k].len, peer = peer[k], dst = endpoint[peer[k]].
+ *   WG_HS_SEND_COOKIE_REPLIES: entries = wg_hs_admit's replies, n_entries = &wg_hs_admit_summary.n_replies; off =
+ *     80 k + 8, len = replies[k].len, peer = WG_HS_NOPEER, dst = the normalised src[replies[k].index].
+ *   An entry below min(*n_entries, n) without a usable destination (an index >= n_src, a family that is neither 4 nor
+ *   6, a peer at or past max_peers or without an endpoint) is skipped and counted in n_nodst. summary = {bytes,
+ *   n_items, n_nodst}. flags must be 0 (the gate is wg_tx_sendlist's): WG_EINVAL. Three launches. n = 0 writes a zero
+ *   summary. */
+/* 12, the status after WG_PKT_HANDSHAKE: wg_tx_sendlist with WG_SEND_GATE, the descriptor's peer has no endpoint */
+#define WG_PKT_NOENDPOINT (WG_PKT_HANDSHAKE + 1u)
+#define WG_EP_LEARN_RESPONSE 1u /* wg_endpoints_start_batch.flags */
+#define WG_SEND_GATE 1u         /* wg_tx_sendlist_batch.flags */
+#define WG_HS_SEND_RESPONSES 0u /* wg_hs_sendlist_batch.kind */
+#define WG_HS_SEND_INITIATIONS 1u
+#define WG_HS_SEND_COOKIE_REPLIES 2u
+typedef struct wg_tx_item { /* 48 bytes */
+  uint64_t off;             /* into the seal's output buffer (wg_tx_sendlist) or from `entries` (wg_hs_sendlist) */
+  uint32_t len;             /* datagram bytes */
+  uint32_t key_slot;        /* 0xFFFFFFFF: a handshake message */
+  uint32_t peer;
+  uint32_t index;           /* position of the descriptor or entry */
+  wg_hs_src dst;
+} wg_tx_item;
+typedef struct wg_endpoints_start_summary {
+  uint32_t n_sessions, n_learned, n_badsrc, n_nopeer;
+} wg_endpoints_start_summary;
+typedef struct wg_endpoints_start_batch {
+  const void* entries;         /* device: the install's entries */
+  const uint32_t* n_entries;   /* device, or NULL: all n */
+  const uint32_t* inst_status; /* device, n entries: the install's */
+  const uint32_t* send_slot;   /* device, n_slots entries */
+  const uint32_t* recv_slot;   /* device, n_slots entries */
+  const wg_hs_src* src;        /* device, 8-byte aligned, n_src entries, by batch index */
+  wg_endpoints_start_summary* summary; /* device, 16 bytes, 8-byte aligned */
+  uint32_t n, n_slots, n_src;
+  uint32_t source;             /* WG_HS_INSTALL_SESSIONS or WG_HS_INSTALL_ESTABLISHED */
+  uint32_t flags;              /* WG_EP_LEARN_RESPONSE */
+  uint32_t _reserved;
+} wg_endpoints_start_batch;
+typedef struct wg_endpoints_learn_summary {
+  uint32_t n_authentic, n_peers, n_roamed, n_badsrc;
+} wg_endpoints_learn_summary;
+typedef struct wg_endpoints_learn_batch {
+  const wg_pkt* desc;           /* device, 16-byte aligned, n entries */
+  const uint32_t* final_status; /* device, n entries */
+  const wg_hs_src* src;         /* device, 8-byte aligned, n entries, by batch index */
+  uint32_t* roamed;             /* device, roamed_cap entries */
+  wg_endpoints_learn_summary* summary; /* device, 16 bytes, 8-byte aligned */
+  uint32_t n, roamed_cap;
+} wg_endpoints_learn_batch;
+typedef struct wg_tx_sendlist_summary {
+  uint64_t bytes;
+  uint32_t n_items, n_noendpoint;
+} wg_tx_sendlist_summary;
+typedef struct wg_tx_sendlist_batch {
+  wg_pkt* desc;      /* device, 16-byte aligned, n entries; in and out with WG_SEND_GATE */
+  uint32_t* status;  /* device, n entries, or NULL; in and out with WG_SEND_GATE */
+  wg_tx_item* items; /* device, 16-byte aligned, n entries */
+  wg_tx_sendlist_summary* summary; /* device, 16 bytes, 8-byte aligned */
+  uint32_t n;
+  uint32_t flags;    /* WG_SEND_GATE */
+} wg_tx_sendlist_batch;
+typedef struct wg_hs_sendlist_summary {
+  uint64_t bytes;
+  uint32_t n_items, n_nodst;
+} wg_hs_sendlist_summary;
+typedef struct wg_hs_sendlist_batch {
+  const void* entries;       /* device, 16-byte aligned: wg_hs_session[], wg_hs_record[] or wg_hs_cookie_reply[] */
+  const uint32_t* n_entries; /* device, or NULL: all n */
+  const uint32_t* status;    /* device, n entries: wg_hs_initiate's (initiations only) */
+  const uint32_t* peer;      /* device, n entries: wg_hs_initiate's (initiations only) */
+  const wg_hs_src* src;      /* device, 8-byte aligned, n_src entries, by batch index (responses, cookie replies) */
+  wg_tx_item* items;         /* device, 16-byte aligned, n entries */
+  wg_hs_sendlist_summary* summary; /* device, 16 bytes, 8-byte aligned */
+  uint32_t n, n_src;
+  uint32_t kind;             /* WG_HS_SEND_* */
+  uint32_t flags;            /* 0 */
+} wg_hs_sendlist_batch;
+int wg_endpoints_reserve(wg_ctx* ctx, uint32_t max_peers);
+int wg_endpoints_set(wg_ctx* ctx, uint32_t first_peer, uint32_t n, const wg_hs_src* endpoints_host);
+int wg_endpoints_get(wg_ctx* ctx, uint32_t first_peer, uint32_t n, wg_hs_src* endpoints_host);
+int wg_endpoint_slots_set(wg_ctx* ctx, uint32_t first_slot, uint32_t n, const uint32_t* peers_host);
+int wg_endpoint_slots_get(wg_ctx* ctx, uint32_t first_slot, uint32_t n, uint32_t* peers_host);
+int wg_endpoints_start(wg_ctx* ctx, const wg_endpoints_start_batch* batch, void* stream);
+int wg_endpoints_learn(wg_ctx* ctx, const wg_endpoints_learn_batch* batch, void* stream);
+int wg_tx_sendlist(wg_ctx* ctx, const wg_tx_sendlist_batch* batch, void* stream);
+int wg_hs_sendlist(wg_ctx* ctx, const wg_hs_sendlist_batch* batch, void* stream);
+
 int wg_seal1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* pt, uint32_t len, uint8_t* out);
 int wg_open1(wg_ctx* ctx, uint32_t key_slot, uint64_t counter, const uint8_t* in, uint32_t len, uint8_t* pt);
 int wg_pp_config(wg_ctx* ctx, uint32_t waves, uint32_t idle_us);

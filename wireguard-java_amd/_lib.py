@@ -34,6 +34,7 @@ WG_PKT_NOROUTE = 8
 WG_PKT_TOOLONG = 9
 WG_PKT_NOSESSION = 10
 WG_PKT_HANDSHAKE = 11
+WG_PKT_NOENDPOINT = 12
 WG_PKT_FAILED = 255
 WG_QUEUE_MAX_LEN = 16384
 WG_RX_FILTER = 1
@@ -102,6 +103,9 @@ WG_TIMER_PEER_CAN_INITIATE = 1
 WG_TIMERS_RX, WG_TIMERS_TX = 0, 1
 WG_TIMERS_GATE = 1
 WG_TIMERS_RETIRE = 1
+WG_EP_LEARN_RESPONSE = 1
+WG_SEND_GATE = 1
+WG_HS_SEND_RESPONSES, WG_HS_SEND_INITIATIONS, WG_HS_SEND_COOKIE_REPLIES = 0, 1, 2
 WG_HS_TS_OK = 0
 WG_HS_TS_REPLAY = 1
 WG_HS_TS_SUPERSEDED = 2
@@ -441,6 +445,64 @@ class WgTimersSweepBatch(ctypes.Structure):
                 ("initiate_cap", ctypes.c_uint32), ("keepalive_cap", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
+class WgTxItem(ctypes.Structure):
+    """wg_tx_item: one datagram of a send list (wg_tx_sendlist / wg_hs_sendlist)."""
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint32), ("key_slot", ctypes.c_uint32),
+                ("peer", ctypes.c_uint32), ("index", ctypes.c_uint32), ("dst", WgHsSrc)]
+
+
+class WgEndpointsStartSummary(ctypes.Structure):
+    """wg_endpoints_start_summary: totals of one wg_endpoints_start call."""
+    _fields_ = [("n_sessions", ctypes.c_uint32), ("n_learned", ctypes.c_uint32), ("n_badsrc", ctypes.c_uint32),
+                ("n_nopeer", ctypes.c_uint32)]
+
+
+class WgEndpointsStartBatch(ctypes.Structure):
+    """wg_endpoints_start_batch: one wg_endpoints_start call (device pointers)."""
+    _fields_ = [("entries", ctypes.c_void_p), ("n_entries", ctypes.c_void_p), ("inst_status", ctypes.c_void_p),
+                ("send_slot", ctypes.c_void_p), ("recv_slot", ctypes.c_void_p), ("src", ctypes.c_void_p),
+                ("summary", ctypes.c_void_p), ("n", ctypes.c_uint32), ("n_slots", ctypes.c_uint32),
+                ("n_src", ctypes.c_uint32), ("source", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("_reserved", ctypes.c_uint32)]
+
+
+class WgEndpointsLearnSummary(ctypes.Structure):
+    """wg_endpoints_learn_summary: totals of one wg_endpoints_learn call."""
+    _fields_ = [("n_authentic", ctypes.c_uint32), ("n_peers", ctypes.c_uint32), ("n_roamed", ctypes.c_uint32),
+                ("n_badsrc", ctypes.c_uint32)]
+
+
+class WgEndpointsLearnBatch(ctypes.Structure):
+    """wg_endpoints_learn_batch: one wg_endpoints_learn call (device pointers)."""
+    _fields_ = [("desc", ctypes.c_void_p), ("final_status", ctypes.c_void_p), ("src", ctypes.c_void_p),
+                ("roamed", ctypes.c_void_p), ("summary", ctypes.c_void_p), ("n", ctypes.c_uint32),
+                ("roamed_cap", ctypes.c_uint32)]
+
+
+class WgTxSendlistSummary(ctypes.Structure):
+    """wg_tx_sendlist_summary: totals of one wg_tx_sendlist call."""
+    _fields_ = [("bytes", ctypes.c_uint64), ("n_items", ctypes.c_uint32), ("n_noendpoint", ctypes.c_uint32)]
+
+
+class WgTxSendlistBatch(ctypes.Structure):
+    """wg_tx_sendlist_batch: one wg_tx_sendlist call (device pointers)."""
+    _fields_ = [("desc", ctypes.c_void_p), ("status", ctypes.c_void_p), ("items", ctypes.c_void_p),
+                ("summary", ctypes.c_void_p), ("n", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class WgHsSendlistSummary(ctypes.Structure):
+    """wg_hs_sendlist_summary: totals of one wg_hs_sendlist call."""
+    _fields_ = [("bytes", ctypes.c_uint64), ("n_items", ctypes.c_uint32), ("n_nodst", ctypes.c_uint32)]
+
+
+class WgHsSendlistBatch(ctypes.Structure):
+    """wg_hs_sendlist_batch: one wg_hs_sendlist call (device pointers)."""
+    _fields_ = [("entries", ctypes.c_void_p), ("n_entries", ctypes.c_void_p), ("status", ctypes.c_void_p),
+                ("peer", ctypes.c_void_p), ("src", ctypes.c_void_p), ("items", ctypes.c_void_p),
+                ("summary", ctypes.c_void_p), ("n", ctypes.c_uint32), ("n_src", ctypes.c_uint32),
+                ("kind", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
 class WgCompletion(ctypes.Structure):
     """wg_completion: one reaped packet of a wg_queue."""
     _fields_ = [("user", ctypes.c_uint64), ("counter", ctypes.c_uint64), ("data", ctypes.c_void_p),
@@ -467,6 +529,9 @@ assert ctypes.sizeof(WgHsInstallSummary) == 16 and ctypes.sizeof(WgHsInstallBatc
 assert ctypes.sizeof(WgTimersConfig) == 64 and ctypes.sizeof(WgTimerSlot) == 48 and ctypes.sizeof(WgTimerPeer) == 16
 assert ctypes.sizeof(WgTimerPeerState) == 24 and ctypes.sizeof(WgTimersStartBatch) == 64
 assert ctypes.sizeof(WgTimersMarkBatch) == 56 and ctypes.sizeof(WgTimersSweepBatch) == 80
+assert ctypes.sizeof(WgTxItem) == 48 and ctypes.sizeof(WgEndpointsStartBatch) == 80 and ctypes.sizeof(WgEndpointsLearnBatch) == 48
+assert ctypes.sizeof(WgTxSendlistBatch) == 40 and ctypes.sizeof(WgHsSendlistBatch) == 72 and ctypes.sizeof(WgTxSendlistSummary) == 16
+assert ctypes.sizeof(WgEndpointsStartSummary) == 16 and ctypes.sizeof(WgEndpointsLearnSummary) == 16 and ctypes.sizeof(WgHsSendlistSummary) == 16
 assert ctypes.sizeof(WgHsStampSummary) == 16 and ctypes.sizeof(WgHsStampBatch) == 80
 assert ctypes.sizeof(WgHsSrc) == 24 and ctypes.sizeof(WgHsCookieReply) == 80 and ctypes.sizeof(WgHsAdmitSummary) == 16
 assert ctypes.sizeof(WgHsAdmitBatch) == 112 and ctypes.sizeof(WgHsLearned) == 16 and ctypes.sizeof(WgHsCookieOpenSummary) == 16
@@ -546,6 +611,15 @@ SIGNATURES = [
     ("wg_timers_start", _I, [_VP, ctypes.POINTER(WgTimersStartBatch), _VP]),
     ("wg_timers_mark", _I, [_VP, ctypes.POINTER(WgTimersMarkBatch), _VP]),
     ("wg_timers_sweep", _I, [_VP, ctypes.POINTER(WgTimersSweepBatch), _VP]),
+    ("wg_endpoints_reserve", _I, [_VP, _U32]),
+    ("wg_endpoints_set", _I, [_VP, _U32, _U32, _VP]),
+    ("wg_endpoints_get", _I, [_VP, _U32, _U32, _VP]),
+    ("wg_endpoint_slots_set", _I, [_VP, _U32, _U32, _VP]),
+    ("wg_endpoint_slots_get", _I, [_VP, _U32, _U32, _VP]),
+    ("wg_endpoints_start", _I, [_VP, ctypes.POINTER(WgEndpointsStartBatch), _VP]),
+    ("wg_endpoints_learn", _I, [_VP, ctypes.POINTER(WgEndpointsLearnBatch), _VP]),
+    ("wg_tx_sendlist", _I, [_VP, ctypes.POINTER(WgTxSendlistBatch), _VP]),
+    ("wg_hs_sendlist", _I, [_VP, ctypes.POINTER(WgHsSendlistBatch), _VP]),
     ("wg_seal1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_open1", _I, [_VP, _U32, _U64, _VP, _U32, _VP]),
     ("wg_pp_config", _I, [_VP, _U32, _U32]),

@@ -101,6 +101,7 @@ struct TxState;  // wg_tx.hip
 struct RxPlanState;  // wg_rxplan.hip
 struct HsState;  // wg_hs.hip
 struct TimersState;  // wg_timers.hip
+struct EndpointsState;  // wg_endpoints.hip
 
 }  // namespace
 
@@ -182,6 +183,7 @@ struct wg_ctx {
   RxPlanState* rxp = nullptr;  // receive-side planning: session table, scratch (wg_rxplan.hip)
   HsState* hs = nullptr;  // handshake: mac1 key, static private key, peers, scratch (wg_hs.hip, wg_x25519.hip, wg_hs_open.hip)
   TimersState* tm = nullptr;  // session timers: slot and peer records, configuration, scratch (wg_timers.hip)
+  EndpointsState* ep = nullptr;  // endpoints: per-peer address, per-slot peer, scratch (wg_endpoints.hip)
   // timing
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -825,6 +827,7 @@ int launch_after_seal(wg_ctx* c, const wg_batch* sb, const wg_batch* ob, hipStre
 #include "wg_hs_stamp.hip"
 #include "wg_hs_cookie.hip"
 #include "wg_timers.hip"
+#include "wg_endpoints.hip"
 
 extern "C" {
 
@@ -950,6 +953,7 @@ int wg_ctx_destroy(wg_ctx* c) {
   rxp_free(c);
   hs_free(c);
   tm_free(c);
+  ep_free(c);
   if (c->keys) {
     (void)hipDeviceSynchronize();  // no launch of this context may still read the table
     (void)hipMemsetAsync(c->keys, 0, (size_t)c->key_slots * 32, c->stream);  // SymmetricKeypair.clean zeroes keys

@@ -53,6 +53,8 @@ WG_HS_ESTABLISHED_DTYPE = np.dtype([("index", "<u4"), ("record", "<u4"), ("pendi
 WG_HS_SRC_DTYPE = np.dtype([("addr", "u1", (16,)), ("port", "u1", (2,)), ("family", "u1"), ("_pad", "u1", (5,))])
 WG_HS_COOKIE_REPLY_DTYPE = np.dtype([("index", "<u4"), ("len", "<u4"), ("msg", "u1", (64,)), ("_pad", "<u4", (2,))])
 WG_HS_LEARNED_DTYPE = np.dtype([("index", "<u4"), ("pending", "<u4"), ("peer", "<u4"), ("_zero", "<u4")])
+WG_TX_ITEM_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("key_slot", "<u4"), ("peer", "<u4"), ("index", "<u4"),
+                             ("dst", WG_HS_SRC_DTYPE)])
 WG_TIMER_SLOT_DTYPE = np.dtype([("state", "<u4"), ("peer", "<u4"), ("local_index", "<u4"), ("partner", "<u4"),
                                 ("born", "<u8"), ("last", "<u8"), ("last_data", "<u8"), ("superseded", "<u8")])
 WG_TIMER_PEER_DTYPE = np.dtype([("keepalive_interval", "<u8"), ("flags", "<u4"), ("_zero", "<u4")])
@@ -479,6 +481,108 @@ class Engine:
                           wire_base=wire_base, retire=retire, stream=st)
         if keepalives.shape[0]:
             self.seal(keepalives, out, out, 16, stream=st, frame=True)
+
+    # ---- endpoints and send lists (wg_endpoints_*, wg_tx_sendlist, wg_hs_sendlist) --------------
+    def endpoints_reserve(self, max_peers: int) -> None:
+        """wg_endpoints_reserve: one endpoint per peer, one peer per key slot, and the send lists' scratch. Needed
+        before every other endpoints_* / *_sendlist call."""
+        L.check(self._lib.wg_endpoints_reserve(self.ctx, max_peers))
+
+    def endpoints_set(self, first_peer: int, endpoints) -> None:
+        """wg_endpoints_set: endpoints = a WG_HS_SRC_DTYPE array, or a list of (address string or ipaddress object,
+        port) pairs and None (no endpoint), from first_peer on. Captured calls see them without re-capture."""
+        if isinstance(endpoints, np.ndarray):
+            v = np.ascontiguousarray(endpoints, dtype=WG_HS_SRC_DTYPE)
+        else:
+            import ipaddress
+            v = np.zeros(len(endpoints), WG_HS_SRC_DTYPE)
+            for k, e in enumerate(endpoints):
+                if e is None:
+                    continue
+                a = ipaddress.ip_address(e[0]) if isinstance(e[0], str) else e[0]
+                v["addr"][k, :len(a.packed)] = np.frombuffer(a.packed, np.uint8)
+                v["port"][k] = (e[1] >> 8, e[1] & 255)
+                v["family"][k] = 4 if a.version == 4 else 6
+        L.check(self._lib.wg_endpoints_set(self.ctx, first_peer, len(v), v.ctypes.data if len(v) else None))
+
+    def endpoints_get(self, first_peer: int, n: int) -> np.ndarray:
+        """wg_endpoints_get: the endpoints of peers [first_peer, first_peer + n), after everything queued
+        (WG_HS_SRC_DTYPE array; family 0: none)."""
+        v = np.zeros(max(n, 1), WG_HS_SRC_DTYPE)
+        L.check(self._lib.wg_endpoints_get(self.ctx, first_peer, n, v.ctypes.data))
+        return v[:n]
+
+    def endpoint_slots_set(self, first_slot: int, peers) -> None:
+        """wg_endpoint_slots_set: the peers of key slots [first_slot, first_slot + len(peers)), for sessions keyed
+        with set_keys() (hs_install() + endpoints_start() set them on the device)."""
+        v = np.ascontiguousarray(np.asarray(peers, dtype=np.uint32))
+        L.check(self._lib.wg_endpoint_slots_set(self.ctx, first_slot, len(v), v.ctypes.data if len(v) else None))
+
+    def endpoint_slots_get(self, first_slot: int, n: int) -> np.ndarray:
+        """wg_endpoint_slots_get: the key slots' peers (uint32 array; WG_HS_NOPEER: none)."""
+        v = np.zeros(max(n, 1), np.uint32)
+        L.check(self._lib.wg_endpoint_slots_get(self.ctx, first_slot, n, v.ctypes.data))
+        return v[:n]
+
+    def endpoints_start(self, entries, summary_n, inst_status, send_slot, recv_slot, src, summary, source: int,
+                        learn_response: bool = False, stream: int | None = None) -> None:
+        """wg_endpoints_start over the tensors hs_install() was given, behind it on the same stream; src uint8
+        [n_src, 24] (the ring's wg_hs_src by batch index) or None, summary int32 [4] (sessions, learned, bad source,
+        no peer)."""
+        n_src = src.shape[0] if src is not None else 0
+        b = L.WgEndpointsStartBatch(entries.data_ptr(), summary_n.data_ptr() if summary_n is not None else None,
+                                    inst_status.data_ptr(), send_slot.data_ptr() if send_slot.shape[0] else None,
+                                    recv_slot.data_ptr() if recv_slot.shape[0] else None, src.data_ptr() if n_src else None,
+                                    summary.data_ptr(), entries.shape[0], send_slot.shape[0], n_src, source,
+                                    L.WG_EP_LEARN_RESPONSE if learn_response else 0, 0)
+        L.check(self._lib.wg_endpoints_start(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def endpoints_learn(self, desc, final_status, src, roamed, summary, stream: int | None = None) -> None:
+        """wg_endpoints_learn over torch tensors, after rx_deliver(): desc int64 [n, 4], final_status int32 [n], src
+        uint8 [n, 24] by batch index, roamed int32 [cap] (the peers whose endpoint moved, ascending), summary int32 [4]
+        (authentic, peers, roamed, bad source)."""
+        n = desc.shape[0]
+        b = L.WgEndpointsLearnBatch(desc.data_ptr() if n else None, final_status.data_ptr() if n else None,
+                                    src.data_ptr() if n else None, roamed.data_ptr() if roamed.shape[0] else None,
+                                    summary.data_ptr(), n, roamed.shape[0])
+        L.check(self._lib.wg_endpoints_learn(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def tx_sendlist(self, desc, status, items, summary, gate: bool = False, stream: int | None = None) -> None:
+        """wg_tx_sendlist over torch tensors: desc int64 [n, 4] and status int32 [n] as tx_plan() left them (status
+        None over timers_sweep()'s keepalives), items uint8 [n, 48] (wg_tx_item: off, len, key slot, peer, index,
+        destination), summary int64 [2] (bytes, n_items | n_noendpoint << 32). gate=True, before the seal only, refuses
+        the descriptors whose peer has no endpoint."""
+        n = desc.shape[0]
+        b = L.WgTxSendlistBatch(desc.data_ptr() if n else None, status.data_ptr() if n and status is not None else None,
+                                items.data_ptr() if n else None, summary.data_ptr(), n, L.WG_SEND_GATE if gate else 0)
+        L.check(self._lib.wg_tx_sendlist(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def hs_sendlist(self, kind: int, entries, summary_n, items, summary, src=None, status=None, peer=None,
+                    stream: int | None = None) -> None:
+        """wg_hs_sendlist over torch tensors: kind WG_HS_SEND_RESPONSES (entries = hs_respond()'s sessions, src),
+        WG_HS_SEND_INITIATIONS (entries = hs_initiate()'s records, with its status and peer) or
+        WG_HS_SEND_COOKIE_REPLIES (entries = hs_admit()'s replies, src); summary_n the tensor whose first word is the
+        entries' number on the device, or None; items uint8 [n, 48] with off relative to entries; summary int64 [2]
+        (bytes, n_items | n_nodst << 32)."""
+        n = entries.shape[0]
+        n_src = src.shape[0] if src is not None else 0
+        b = L.WgHsSendlistBatch(entries.data_ptr() if n else None, summary_n.data_ptr() if summary_n is not None else None,
+                                status.data_ptr() if n and status is not None else None,
+                                peer.data_ptr() if n and peer is not None else None, src.data_ptr() if n_src else None,
+                                items.data_ptr() if n else None, summary.data_ptr(), n, n_src, kind, 0)
+        L.check(self._lib.wg_hs_sendlist(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def tx_send(self, tun, pkt_off, pkt_len, desc_out, tx_status, out, items, send_summary, wire_stride: int,
+                max_len: int, route: bool = False, wire_base: int = 0, uniform: bool = False,
+                stream: int | None = None) -> None:
+        """tun ring -> UDP ring and its send list on one stream: tx_plan, tx_sendlist with the gate (a packet whose
+        peer has no endpoint is not sealed), seal(frame=True). The host sends items[:n_items] with sendmmsg and reads
+        nothing else back."""
+        st = stream if stream is not None else _torch_stream()
+        self.tx_plan(tun, pkt_off, pkt_len, desc_out, tx_status, wire_stride, out.numel(), max_len, route=route,
+                     wire_base=wire_base, stream=st)
+        self.tx_sendlist(desc_out, tx_status, items, send_summary, gate=True, stream=st)
+        self.seal(desc_out, tun, out, max_len, uniform=uniform, stream=st, frame=True)
 
     def rx_plan(self, wire, pkt_off, pkt_len, desc_out, rx_status, host_list, summary, max_len: int,
                 packed: bool = False, pt_base: int = 0, pt_size: int = 0, stream: int | None = None) -> None:
