@@ -1269,8 +1269,9 @@ int wg_hs_mac2(wg_ctx* ctx, const wg_hs_mac2_batch* batch, void* stream);
  *   entry, so equal indices in one call retire it once. *n_retired_dev (device, 4-byte aligned, may be NULL) =
  *   the number of entries the call retired. There is no per-position status: nothing depends on thread order.
  *   A retired index plans as WG_PKT_NOSESSION; the entries behind it in its probe sequence are still found.
- *   `used` does not fall: only a rebuild (wg_rx_sessions_set, wg_rx_sessions_reserve) reclaims retired entries.
- *   The keys are not touched: wg_keys_zero stays the host's call.
+ *   `used` does not fall: a rebuild (wg_rx_sessions_set, wg_rx_sessions_reserve) reclaims retired entries, and so
+ *   does wg_rx_sessions_compact on the device ("the end of a session on the device", below).
+ *   The keys are not touched: wg_keys_zero is the host's call, WG_TIMERS_WIPE the sweep's.
  * wg_rx_sessions_count(ctx, &live, &retired): synchronous, after everything queued on the device (either
  *   pointer may be NULL).
  *
@@ -1330,6 +1331,8 @@ int wg_hs_mac2(wg_ctx* ctx, const wg_hs_mac2_batch* batch, void* stream);
 #define WG_HS_INSTALL_SESSIONS 0u    /* source: wg_hs_session[] */
 #define WG_HS_INSTALL_ESTABLISHED 1u /* source: wg_hs_established[] */
 #define WG_HS_INSTALL_WIPE 1u        /* flags: zero an installed entry's send_key and recv_key */
+#define WG_HS_INSTALL_COMPACT 4u     /* flags: compact the table first if the ring would not fit ("the end of a session on
+                                        the device"). 4, not 2: flags == 2 and 0x80000001 stay WG_EINVAL */
 typedef struct wg_hs_install_summary {
   uint32_t n_ok, n_badslot, n_dup, n_full;
 } wg_hs_install_summary;
@@ -1344,7 +1347,7 @@ typedef struct wg_hs_install_batch {
   uint32_t n, n_slots;
   uint32_t slot_first, slot_count; /* the device-owned slot range of this call */
   uint32_t source;           /* WG_HS_INSTALL_SESSIONS or WG_HS_INSTALL_ESTABLISHED */
-  uint32_t flags;            /* WG_HS_INSTALL_WIPE */
+  uint32_t flags;            /* WG_HS_INSTALL_WIPE | WG_HS_INSTALL_COMPACT */
 } wg_hs_install_batch;
 int wg_rx_sessions_reserve(wg_ctx* ctx, uint32_t max_sessions);
 int wg_rx_sessions_retire(wg_ctx* ctx, const uint32_t* indices_dev, uint32_t n, uint32_t* n_retired_dev, void* stream);
@@ -1457,6 +1460,7 @@ int wg_hs_install(wg_ctx* ctx, const wg_hs_install_batch* batch, void* stream);
 #define WG_TIMERS_TX 1u
 #define WG_TIMERS_GATE 1u             /* wg_timers_mark_batch.flags */
 #define WG_TIMERS_RETIRE 1u           /* wg_timers_sweep_batch.flags */
+#define WG_TIMERS_WIPE 2u             /* wg_timers_sweep_batch.flags, with RETIRE only: zero the retired sessions' keys */
 typedef struct wg_timers_config { /* 64 bytes; 0 = off */
   uint64_t rekey_after_time, reject_after_time, rekey_timeout, keepalive_timeout, linger;
   uint64_t rekey_after_messages, reject_after_messages;
@@ -1515,7 +1519,7 @@ typedef struct wg_timers_sweep_batch {
   wg_timers_sweep_summary* summary; /* device, 32 bytes, 8-byte aligned */
   uint64_t wire_base, wire_stride, out_size; /* the keepalives' wire slots, as in wg_tx_batch */
   uint32_t expired_cap, initiate_cap, keepalive_cap;
-  uint32_t flags;                   /* WG_TIMERS_RETIRE */
+  uint32_t flags;                   /* WG_TIMERS_RETIRE | WG_TIMERS_WIPE */
 } wg_timers_sweep_batch;
 int wg_timers_reserve(wg_ctx* ctx, uint32_t max_peers);
 int wg_timers_config_set(wg_ctx* ctx, const wg_timers_config* config);
@@ -1525,6 +1529,63 @@ int wg_timers_peers_get(wg_ctx* ctx, uint32_t first_peer, uint32_t n, wg_timer_p
 int wg_timers_start(wg_ctx* ctx, const wg_timers_start_batch* batch, void* stream);
 int wg_timers_mark(wg_ctx* ctx, const wg_timers_mark_batch* batch, void* stream);
 int wg_timers_sweep(wg_ctx* ctx, const wg_timers_sweep_batch* batch, void* stream);
+
+/* ---- the end of a session on the device ----
+ * What the reference does when a session ends, EstablishedSession.close() -> keypair.clean()
+ * (EstablishedSession.java:74-77, SymmetricKeypair.java:85-93: both keys are zeroed), and what a table that only
+ * fills needs besides: the retired entries of the receiver-index table are reclaimed, and an expired session's keys
+ * are zeroed, without a host round trip. All of it is opt-in: a context that uses none of it behaves as before.
+ *
+ * wg_rx_sessions_compact(ctx, min_retired, summary_dev, stream): asynchronous on `stream` and capturable; it waits
+ *   for, and is waited for by, the receive plans, installs and retires of every stream, as wg_rx_sessions_retire
+ *   does. On the device: if used - count (the retired entries) >= max(min_retired, 1), the table is rebuilt from its
+ *   live entries; afterwards used == count, every live index resolves to the key slot it resolved to before and
+ *   every other index is absent. Otherwise nothing changes. summary (device, 16 bytes, 8-byte aligned, may be NULL)
+ *   = {live, dropped, compacted, 0}: {count, the retired entries dropped, 1, 0} or {count, 0, 0, 0}.
+ *   Without wg_rx_sessions_reserve: WG_EINVAL. NULL context, misaligned summary: WG_EINVAL.
+ *   The live entries are rehashed into a second buffer of the table's capacity, which wg_rx_sessions_reserve
+ *   allocates (a capturing stream cannot) and wg_rx_sessions_set keeps at the capacity of the table it builds, and
+ *   the header's pointer is flipped: every kernel reads the entries through the header. The two buffers' addresses
+ *   sit at a fixed device address and which of them is the spare is decided on the device, so nothing about a call
+ *   lives on the host or in the launch: a captured compaction replays any number of times, and after a
+ *   wg_rx_sessions_set that grew the table and moved the buffers. A wg_rx_sessions_set or wg_rx_sessions_reserve
+ *   that returned an error (an allocation failed: the table is empty and the reserve is gone, and with the spare
+ *   there are two allocations that can fail) is the exception: a compaction or an install captured before it
+ *   must be captured again after the next successful wg_rx_sessions_reserve.
+ *   Three launches, ordered by kernel boundaries, no workgroup waiting for another: the whole spare is cleared (in
+ *   every call: it holds the table of two compactions ago) and one thread decides; one thread per bucket of the
+ *   current table places a live entry by a 64-bit compare-and-swap against 0 along its probe sequence in the spare
+ *   (live indices are unique); one thread flips the pointer, sets used = count and writes the summary. Which
+ *   bucket of a chain an entry lands in depends on thread order; no lookup, count or later status does.
+ *
+ * WG_HS_INSTALL_COMPACT (wg_hs_install_batch.flags): the same compaction, decided on the device in front of the
+ *   install's step 3. With m = min(*n_entries, n): if used + m > C / 2 and used > count, the table is compacted
+ *   first (the three launches above, in front of the install's own). Statuses and summary are exactly those of
+ *   wg_rx_sessions_compact followed by the plain install: step 4's `used` is the compacted table's, so FULL then
+ *   means live + passing > C / 2. A captured ... -> wg_hs_respond -> wg_hs_install still replays.
+ *
+ * WG_TIMERS_WIPE (wg_timers_sweep_batch.flags; only together with WG_TIMERS_RETIRE, alone it is WG_EINVAL): for
+ *   every session the sweep lists and retires, the 32 key bytes of its send slot and of its recv slot (if that is
+ *   inside the key table) are zeroed, by stores of zero only: no key byte is loaded. A session that is due but does
+ *   not fit expired_cap is neither listed nor wiped and stays due. Every output and the summary are what they are
+ *   without the flag.
+ *   - The key table has no ordering with seals and opens on other streams, as for wg_hs_install: sweep on the stream
+ *     that seals and opens next, or synchronise.
+ *   - An all-zero key is a known key. A wiped send slot must never be sealed on again: wg_timers_mark(WG_TIMERS_TX,
+ *     WG_TIMERS_GATE) refuses its descriptors, because the record is DEAD.
+ *   - A wiped recv slot must never be opened on again: its index is retired in the receiver-index table, so
+ *     wg_rx_plan answers WG_PKT_NOSESSION.
+ *   - The host's mirror of the key table (wg_seal1 / wg_open1, the queues) is not touched: the sweep's slots are
+ *     known on the device only. Slots written by wg_hs_install have no key in the mirror already (those paths answer
+ *     WG_ENOKEY). A slot whose key the host set with wg_keys_set keeps that key in host memory, and the per-packet
+ *     paths go on using it, until the host calls wg_keys_zero or wg_keys_set on it: wipe sessions whose keys came
+ *     through wg_hs_install, or follow the expired list with wg_keys_zero.
+ *   - Open: a session killed by wg_timers_start because one of its slots was reused keeps the key in its other slot
+ *     until that slot is reused or the host calls wg_keys_zero. */
+typedef struct wg_rx_compact_summary { /* 16 bytes */
+  uint32_t live, dropped, compacted, _zero;
+} wg_rx_compact_summary;
+int wg_rx_sessions_compact(wg_ctx* ctx, uint32_t min_retired, wg_rx_compact_summary* summary_dev, void* stream);
 
 /* ---- endpoints on the device: learn, roam, and the send lists ----
  * Where a sealed datagram goes. The reference gives every session one address, EstablishedSession.

@@ -96,6 +96,7 @@ WG_HS_INST_FULL = 4
 WG_HS_INSTALL_SESSIONS = 0
 WG_HS_INSTALL_ESTABLISHED = 1
 WG_HS_INSTALL_WIPE = 1
+WG_HS_INSTALL_COMPACT = 4
 WG_TIMER_NONE, WG_TIMER_SEND_INITIATOR, WG_TIMER_SEND_RESPONDER, WG_TIMER_RECV, WG_TIMER_DEAD = 0, 1, 2, 3, 4
 WG_TIMER_NOSLOT = 0xFFFFFFFF
 WG_TIMERS_INITIATOR_ONLY = 1
@@ -103,6 +104,7 @@ WG_TIMER_PEER_CAN_INITIATE = 1
 WG_TIMERS_RX, WG_TIMERS_TX = 0, 1
 WG_TIMERS_GATE = 1
 WG_TIMERS_RETIRE = 1
+WG_TIMERS_WIPE = 2
 WG_EP_LEARN_RESPONSE = 1
 WG_SEND_GATE = 1
 WG_HS_SEND_RESPONSES, WG_HS_SEND_INITIATIONS, WG_HS_SEND_COOKIE_REPLIES = 0, 1, 2
@@ -395,6 +397,12 @@ class WgHsInstallBatch(ctypes.Structure):
                 ("flags", ctypes.c_uint32)]
 
 
+class WgRxCompactSummary(ctypes.Structure):
+    """wg_rx_compact_summary: what one wg_rx_sessions_compact call found and did."""
+    _fields_ = [("live", ctypes.c_uint32), ("dropped", ctypes.c_uint32), ("compacted", ctypes.c_uint32),
+                ("_zero", ctypes.c_uint32)]
+
+
 class WgTimersConfig(ctypes.Structure):
     """wg_timers_config: the session timers' limits in ticks and messages (0 = off)."""
     _fields_ = [("rekey_after_time", ctypes.c_uint64), ("reject_after_time", ctypes.c_uint64),
@@ -526,6 +534,7 @@ assert ctypes.sizeof(WgX25519Desc) == 32 and ctypes.sizeof(WgHsDhBatch) == 40
 assert ctypes.sizeof(WgHsInit) == 144 and ctypes.sizeof(WgHsOpenSummary) == 16 and ctypes.sizeof(WgHsOpenBatch) == 64
 assert ctypes.sizeof(WgHsSession) == 176 and ctypes.sizeof(WgHsRespondSummary) == 16 and ctypes.sizeof(WgHsRespondBatch) == 64
 assert ctypes.sizeof(WgHsInstallSummary) == 16 and ctypes.sizeof(WgHsInstallBatch) == 80
+assert ctypes.sizeof(WgRxCompactSummary) == 16
 assert ctypes.sizeof(WgTimersConfig) == 64 and ctypes.sizeof(WgTimerSlot) == 48 and ctypes.sizeof(WgTimerPeer) == 16
 assert ctypes.sizeof(WgTimerPeerState) == 24 and ctypes.sizeof(WgTimersStartBatch) == 64
 assert ctypes.sizeof(WgTimersMarkBatch) == 56 and ctypes.sizeof(WgTimersSweepBatch) == 80
@@ -602,6 +611,7 @@ SIGNATURES = [
     ("wg_rx_sessions_reserve", _I, [_VP, _U32]),
     ("wg_rx_sessions_retire", _I, [_VP, _VP, _U32, _VP, _VP]),
     ("wg_rx_sessions_count", _I, [_VP, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    ("wg_rx_sessions_compact", _I, [_VP, _U32, _VP, _VP]),
     ("wg_hs_install", _I, [_VP, ctypes.POINTER(WgHsInstallBatch), _VP]),
     ("wg_timers_reserve", _I, [_VP, _U32]),
     ("wg_timers_config_set", _I, [_VP, ctypes.POINTER(WgTimersConfig)]),

@@ -28,6 +28,10 @@
 //                  entry is emptied again (nothing else was written). Otherwise the candidate's entry becomes
 //                  {index, recv slot + 1}, its keys are copied, its counters and windows cleared (256 lanes over
 //                  up to 2 x 8 KiB of window), and workgroup 0 adds the candidates to `used`.
+// With WG_HS_INSTALL_COMPACT the three launches of wg_rx_sessions_compact (wg_rxplan.hip) run in front of these five:
+// if the ring's m = min(*n_entries, n) entries would not fit (used + m > C / 2) and the table holds retired entries,
+// it is rebuilt from its live ones first, and k_inst_fill takes used0 from the compacted table. Statuses and summary
+// are those of compacting first and installing after.
 // More entries than the table has empty buckets (a reserve far too small for the ring) cannot all be placed: an
 // entry that has walked the whole table without finding its index or an empty bucket knows that no bucket will
 // ever hold its index (an occupied bucket never changes its index during the call), so the lowest of such
@@ -243,7 +247,7 @@ extern "C" {
 
 int wg_hs_install(wg_ctx* c, const wg_hs_install_batch* b, void* stream) {
   if (!c || !b) return fail(WG_EINVAL, "NULL argument");
-  if (b->flags & ~WG_HS_INSTALL_WIPE) return fail(WG_EINVAL, "unknown install flags 0x%x", b->flags);
+  if (b->flags & ~(WG_HS_INSTALL_WIPE | WG_HS_INSTALL_COMPACT)) return fail(WG_EINVAL, "unknown install flags 0x%x", b->flags);
   if (b->source != WG_HS_INSTALL_SESSIONS && b->source != WG_HS_INSTALL_ESTABLISHED)
     return fail(WG_EINVAL, "unknown install source %u", b->source);
   if (((uintptr_t)b->n_entries) & 3u) return fail(WG_EINVAL, "n_entries must be 4-byte aligned");
@@ -316,6 +320,13 @@ int wg_hs_install(wg_ctx* c, const wg_hs_install_batch* b, void* stream) {
   P.bits = r ? (uint64_t*)r->d_bits.p : nullptr;
   P.words = r ? r->window / 64u : 0u;
   const uint32_t nb = rank_blocks(n);
+  if (b->flags & WG_HS_INSTALL_COMPACT) {  // decided on the device, in front of k_inst_fill: used0 is the compacted table's
+    wgrp::RxCompactParams Q{};
+    Q.n_entries = b->n_entries;
+    Q.n = n;
+    Q.install = 1u;
+    rxp_compact_launch(t, s, Q);
+  }
   hipLaunchKernelGGL(wgin::k_inst_fill, dim3(std::max(1u, rank_blocks(hi - lo))), dim3(256), 0, s, P, lo, hi);
   hipLaunchKernelGGL(wgin::k_inst_claim, dim3(nb), dim3(256), 0, s, P);
   hipLaunchKernelGGL(wgin::k_inst_insert, dim3(nb), dim3(256), 0, s, P);

@@ -22,9 +22,24 @@
 // A table the device can change. wg_rx_sessions_reserve gives the table a fixed capacity C of the context's
 // own entries; wg_hs_install (wg_hs_install.hip) then inserts into it and wg_rx_sessions_retire turns a live
 // entry into a retired one, {index, 0xFFFFFFFF}: not empty (a probe walk goes on behind it), not a match.
-// `used` counts live + retired entries and never exceeds C / 2, which bounds every walk; only a rebuild on the
-// host (wg_rx_sessions_set, wg_rx_sessions_reserve) drops the retired ones. A context that never reserves
-// builds exactly the tables it built before there was a reserve.
+// `used` counts live + retired entries and never exceeds C / 2, which bounds every walk; a rebuild on the
+// host (wg_rx_sessions_set, wg_rx_sessions_reserve) drops the retired ones, and so does wg_rx_sessions_compact
+// on the device. A context that never reserves builds exactly the tables it built before there was a reserve.
+//
+// Compaction. Every kernel reads the entries through the header, so the live entries are rehashed into a second
+// buffer of the same capacity (the spare, allocated with the reserve) and the header's pointer is flipped; nothing
+// is copied back. Both buffers' addresses sit beside the control words at a fixed device address, and which of
+// them is the spare is decided on the device, by what the header names, so nothing about a call lives on the host
+// and a captured compaction replays in either parity, and after a host rebuild that moved the buffers. Three launches,
+// ordered by kernel boundaries, no workgroup waiting for another:
+//   k_rx_compact_clear   the whole spare = empty (16-B stores), in every call, needed or not: the spare holds the
+//                  table of two compactions ago, and an entry left there would bring a retired index back.
+//                  One thread writes the decision and the counts into the control words.
+//   k_rx_compact_rehash  one thread per bucket of the current table (a wave reads 512 contiguous bytes): a live
+//                  entry claims the first empty bucket of its probe sequence in the spare by a 64-bit
+//                  compare-and-swap against 0. Live indices are unique, so there is nothing to deduplicate;
+//                  which bucket of a chain an entry gets depends on thread order, what a lookup answers does not.
+//   k_rx_compact_flip    one thread: entries = the spare, used = count; the summary.
 //
 // Ranks. The plan needs two stable ranks over the batch (the handshake list, the 64-bit prefix of the
 // packed plaintext offsets) and the deliver one (the item list). Both are a rank_launch of wg_plan.hip,
@@ -62,21 +77,31 @@ struct RxInstCtl {  // wg_hs_install's words between its launches (written by it
   uint32_t used0, n_cand, n_badslot, n_dup;
 };
 
+struct RxCompactCtl {  // at a fixed device address
+  uint32_t go, live, dropped, _pad;  // the compaction's words between its launches (written by its first launch in every call)
+  uint2* buf[2];  // the table's two buffers, written by the host with every table it builds: the header names one,
+                  // the other is the spare. (Here and not in the launch: a captured compaction follows a table that moved.)
+};
+
 struct RxPlanState {
   DevBuf d_hdr;    // RxSessHdr (fixed address)
   DevBuf d_empty;  // 16 empty entries: the table of a context without sessions
-  DevBuf d_ent;    // the entries of the current table
+  DevBuf d_ent;    // the entries a host rebuild writes: the current table, or (after a compaction) the spare
+  DevBuf d_ent2;   // reserved tables only: the other buffer, of the table's capacity (the device knows which is which)
+  uint32_t capacity = 16;  // of the table the host last built (the compaction's grid; its kernels read the header's)
   DevBuf d_code;   // per packet: {status, key slot, counter lo, counter hi}
   DevBuf d_part;   // per workgroup: {bytes lo, bytes hi, count, count}, then their exclusive prefixes
   uint32_t reserved = 0;  // wg_rx_sessions_reserve's capacity C (0: never reserved)
   DevBuf d_claim;  // wg_hs_install: per key slot, the lowest entry that names it
   DevBuf d_ctl;    // wg_hs_install: RxInstCtl
+  DevBuf d_cmp;    // wg_rx_sessions_compact: RxCompactCtl
   StreamOrder order;  // last plan / deliver / table write
 };
 
 const PlanWords kRxPlanWords{"receive plan", "packets", "wg_rx_reserve"};
 const PlanWords kRxDeliverWords{"receive deliver", "packets", "wg_rx_reserve"};
 const PlanWords kRxRetireWords{"session retire", "indices", "wg_rx_sessions_reserve"};
+const PlanWords kRxCompactWords{"session compaction", "entries", "wg_rx_sessions_reserve"};
 
 uint32_t rxp_capacity(uint32_t n) {  // the smallest power of two >= max(16, 4 n)
   uint32_t cap = 16;
@@ -150,17 +175,25 @@ int rxp_table_set(wg_ctx* c, RxPlanState* t, const uint32_t* indices, const uint
   int rc;
   HIPTRY(hipDeviceSynchronize());  // the entries may move: no plan launched earlier (on any stream) may still read them
   if (own) {
-    if ((rc = t->d_ent.ensure(ent.size() * sizeof(uint2))) != WG_OK) {
+    // (a reserved table keeps its spare at the table's capacity: a capturing compaction cannot allocate)
+    if ((rc = t->d_ent.ensure(ent.size() * sizeof(uint2))) != WG_OK ||
+        (t->reserved && (rc = t->d_ent2.ensure(ent.size() * sizeof(uint2))) != WG_OK)) {
       t->reserved = 0;
       rxp_header(t, 0, false, &H);  // the old entries are gone: no sessions, no reserve
       (void)hipMemcpyAsync(t->d_hdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream);
       (void)hipStreamSynchronize(c->stream);
+      t->capacity = 16;
       return rc;
     }
     H.entries = (const uint2*)t->d_ent.p;
     HIPTRY(hipMemcpyAsync(t->d_ent.p, ent.data(), ent.size() * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
+    if (t->reserved) {  // (wg_rx_sessions_reserve has allocated the control block)
+      uint2* const both[2] = {(uint2*)t->d_ent.p, (uint2*)t->d_ent2.p};
+      HIPTRY(hipMemcpyAsync((uint8_t*)t->d_cmp.p + offsetof(RxCompactCtl, buf), both, sizeof both, hipMemcpyHostToDevice, c->stream));
+    }
   }
   HIPTRY(hipMemcpyAsync(t->d_hdr.p, &H, sizeof H, hipMemcpyHostToDevice, c->stream));
+  t->capacity = H.mask + 1u;
   if ((rc = t->order.mark(c->stream)) != WG_OK) return rc;
   HIPTRY(hipStreamSynchronize(c->stream));
   return WG_OK;
@@ -246,6 +279,71 @@ __global__ void __launch_bounds__(256) k_rx_retire(RxSessHdr* hdr, const uint32_
   if (threadIdx.x == 0 && total) {
     atomicSub(&hdr->count, total);
     if (n_retired) atomicAdd(n_retired, total);
+  }
+}
+
+// ---- compaction ----
+struct RxCompactParams {
+  RxSessHdr* hdr;
+  RxCompactCtl* ctl;          // the control words and the table's two buffers
+  wg_rx_compact_summary* summary;  // NULL: none (the install's)
+  const uint32_t* n_entries;  // install: the ring's count on the device (NULL: all n)
+  uint32_t n;                 // install: entries of the ring
+  uint32_t min_retired;       // wg_rx_sessions_compact: the threshold
+  uint32_t install;           // decided by the install's rule instead
+};
+
+__device__ __forceinline__ uint2* rx_spare(const RxCompactParams& P, const uint2* current) {
+  uint2* const b0 = P.ctl->buf[0];
+  return b0 == current ? P.ctl->buf[1] : b0;
+}
+
+// The whole spare = empty, two entries per 16-B store; thread 0 decides. wg_rx_sessions_compact: retired >=
+// max(min_retired, 1). wg_hs_install(COMPACT): the ring would not fit (used + m > C / 2) and there is something to drop.
+__global__ void __launch_bounds__(256) k_rx_compact_clear(RxCompactParams P) {
+  const RxSessHdr H = *P.hdr;
+  uint4* spare = (uint4*)rx_spare(P, H.entries);
+  const uint32_t pairs = (uint32_t)(((uint64_t)H.mask + 1u) / 2u);  // (a capacity is a power of two >= 16)
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < pairs; i += gridDim.x * 256u) spare[i] = make_uint4(0u, 0u, 0u, 0u);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const uint32_t retired = H.used - H.count;
+    bool go;
+    if (P.install) go = retired != 0u && (uint64_t)H.used + dev_count(P.n_entries, P.n) > ((uint64_t)H.mask + 1u) / 2u;
+    else go = retired >= (P.min_retired ? P.min_retired : 1u);
+    *(uint4*)P.ctl = make_uint4(go ? 1u : 0u, H.count, go ? retired : 0u, 0u);
+  }
+}
+
+// One bucket of the current table per thread. Live: a high word that is neither 0 nor retired nor transient (between
+// calls there are no transient entries). The walk is bounded by the capacity; the spare holds at most `count` <= C / 2
+// entries, so it ends long before.
+__global__ void __launch_bounds__(256) k_rx_compact_rehash(RxCompactParams P) {
+  if (!P.ctl->go) return;
+  const RxSessHdr H = *P.hdr;
+  const unsigned long long* cur = (const unsigned long long*)H.entries;
+  unsigned long long* spare = (unsigned long long*)rx_spare(P, H.entries);
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i <= H.mask; i += (uint64_t)gridDim.x * 256u) {
+    const unsigned long long v = cur[i];
+    const uint32_t h = (uint32_t)(v >> 32);
+    if (!h || (h & kRxTransient)) continue;  // (kRxRetired has the transient bit)
+    uint32_t b = mix32((uint32_t)v);
+    for (uint32_t probes = 0; probes <= H.mask; ++probes, ++b)
+      if (atomicCAS(spare + (b & H.mask), 0ull, v) == 0ull) break;
+  }
+}
+
+__global__ void k_rx_compact_flip(RxCompactParams P) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const uint4 w = *(const uint4*)P.ctl;
+  const RxCompactCtl C{w.x, w.y, w.z, 0u, {nullptr, nullptr}};
+  if (C.go) {
+    P.hdr->entries = rx_spare(P, P.hdr->entries);
+    P.hdr->used = C.live;
+  }
+  if (P.summary) {  // (8-B stores: the summary need not be 16-B aligned)
+    uint2* sum = (uint2*)P.summary;
+    sum[0] = make_uint2(C.live, C.dropped);
+    sum[1] = make_uint2(C.go, 0u);
   }
 }
 
@@ -374,8 +472,41 @@ __global__ void __launch_bounds__(256) k_rx_items(RxDeliverParams P) {
 
 }  // namespace wgrp
 
+namespace {
+
+// The compaction's three launches on s, for a reserved table (both buffers and the control block exist). The grids
+// follow the capacity the host last built; the kernels stride over the header's, and take the buffers from the
+// control block, whatever they are when they run.
+void rxp_compact_launch(RxPlanState* t, hipStream_t s, wgrp::RxCompactParams P) {
+  P.hdr = (RxSessHdr*)t->d_hdr.p;
+  P.ctl = (RxCompactCtl*)t->d_cmp.p;
+  hipLaunchKernelGGL(wgrp::k_rx_compact_clear, dim3(std::max(1u, rank_blocks(t->capacity / 2u))), dim3(256), 0, s, P);
+  hipLaunchKernelGGL(wgrp::k_rx_compact_rehash, dim3(std::max(1u, rank_blocks(t->capacity))), dim3(256), 0, s, P);
+  hipLaunchKernelGGL(wgrp::k_rx_compact_flip, dim3(1), dim3(64), 0, s, P);
+}
+
+}  // namespace
+
 // ---- C ABI --------------------------------------------------------------------------------
 extern "C" {
+
+int wg_rx_sessions_compact(wg_ctx* c, uint32_t min_retired, wg_rx_compact_summary* summary_dev, void* stream) {
+  if (!c) return fail(WG_EINVAL, "NULL context");
+  if (((uintptr_t)summary_dev) & 7u) return fail(WG_EINVAL, "summary must be 8-byte aligned");
+  hipStream_t s = pick_stream(c, stream);
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  RxPlanState* t = c->rxp;
+  if (!t || !t->reserved) return fail(WG_EINVAL, "wg_rx_sessions_compact before wg_rx_sessions_reserve");
+  const bool capturing = stream_capturing(s);
+  int rc;
+  if (!capturing && (rc = t->order.after_last(s)) != WG_OK) return rc;
+  wgrp::RxCompactParams P{};
+  P.summary = summary_dev;
+  P.min_retired = min_retired;
+  rxp_compact_launch(t, s, P);
+  return plan_end(t->order, s, capturing, kRxCompactWords);
+}
 
 int wg_rx_sessions_set(wg_ctx* c, const uint32_t* indices, const uint32_t* slots, uint32_t n) {
   if (!c || ((!indices || !slots) && n)) return fail(WG_EINVAL, "NULL argument");
@@ -397,7 +528,9 @@ int wg_rx_sessions_reserve(wg_ctx* c, uint32_t max_sessions) {
   RxPlanState* t;
   int rc;
   if ((rc = rxp_get(c, &t)) != WG_OK) return rc;
-  if ((rc = t->d_claim.ensure((size_t)c->key_slots * 4)) != WG_OK || (rc = t->d_ctl.ensure(sizeof(RxInstCtl))) != WG_OK) return rc;
+  if ((rc = t->d_claim.ensure((size_t)c->key_slots * 4)) != WG_OK || (rc = t->d_ctl.ensure(sizeof(RxInstCtl))) != WG_OK ||
+      (rc = t->d_cmp.ensure(sizeof(RxCompactCtl))) != WG_OK)
+    return rc;
   // the live entries of the current table, in table order (retired ones are dropped by the rebuild)
   HIPTRY(hipDeviceSynchronize());
   RxSessHdr H;

@@ -10,7 +10,7 @@
 //   wg_timers_start  behind wg_hs_install: the records of the sessions it installed; the peer's current session.
 //   wg_timers_mark   behind wg_rx_deliver / wg_tx_plan: proof of life per key slot, and the gate that refuses a
 //                    descriptor on a session that is dead or past its limits.
-//   wg_timers_sweep  the tick: the expired sessions (and their retirement), the peers to initiate to in
+//   wg_timers_sweep  the tick: the expired sessions (their retirement, and with WIPE their keys zeroed), the peers to initiate to in
 //                    wg_hs_initiate's format, the keepalives as ready wg_pkt descriptors.
 // Nothing per packet or per session crosses to the host, and nothing about a call lives on the host: a captured
 // chain replays with `now` refreshed in place.
@@ -240,6 +240,7 @@ struct TmSweepParams {
   uint64_t wire_base, wire_stride;
   uint32_t N, cap_exp, cap_init, cap_keep, retire;
   uint32_t pad_keep;  // the keepalive array's own capacity (cap_keep: what of it has a wire slot)
+  uint4* keys;        // WIPE: the key table, two 16-B words per slot (NULL: no wipe)
 };
 
 __global__ void __launch_bounds__(256) k_tm_sweep_judge(TmSweepParams P) {
@@ -331,6 +332,15 @@ __global__ void __launch_bounds__(256) k_tm_sweep_place(TmSweepParams P, uint32_
       T.slots[g].state = WG_TIMER_DEAD;
       if (h.w < T.K) T.slots[h.w].state = WG_TIMER_DEAD;
       if (h.y < T.max_peers && T.peers[h.y].current == g) T.peers[h.y].current = WG_TIMER_NOSLOT;
+      if (P.keys) {  // the session's two keys: stores of zero, no key byte is loaded
+        const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+        P.keys[2u * g] = z;
+        P.keys[2u * g + 1u] = z;
+        if (h.w < T.K) {
+          P.keys[2u * h.w] = z;
+          P.keys[2u * h.w + 1u] = z;
+        }
+      }
     }
   }
   if ((code & kInit) && pre.z + ri < P.cap_init) {
@@ -561,7 +571,8 @@ int wg_timers_mark(wg_ctx* c, const wg_timers_mark_batch* b, void* stream) {
 
 int wg_timers_sweep(wg_ctx* c, const wg_timers_sweep_batch* b, void* stream) {
   if (!c || !b) return fail(WG_EINVAL, "NULL argument");
-  if (b->flags & ~WG_TIMERS_RETIRE) return fail(WG_EINVAL, "unknown sweep flags 0x%x", b->flags);
+  if ((b->flags & ~(WG_TIMERS_RETIRE | WG_TIMERS_WIPE)) || ((b->flags & WG_TIMERS_WIPE) && !(b->flags & WG_TIMERS_RETIRE)))
+    return fail(WG_EINVAL, "unknown sweep flags 0x%x (the wipe goes with the retire)", b->flags);
   if (!b->now || (((uintptr_t)b->now) & 7u)) return fail(WG_EINVAL, "now must be non-NULL and 8-byte aligned");
   if (!b->summary || (((uintptr_t)b->summary) & 7u)) return fail(WG_EINVAL, "summary must be non-NULL and 8-byte aligned");
   if ((b->expired_cap && (!b->expired || (((uintptr_t)b->expired) & 15u))) || (b->initiate_cap && (!b->initiate || (((uintptr_t)b->initiate) & 3u))) ||
@@ -605,6 +616,7 @@ int wg_timers_sweep(wg_ctx* c, const wg_timers_sweep_batch* b, void* stream) {
   P.cap_keep = (uint32_t)std::min<uint64_t>(b->keepalive_cap, wire_slots);
   P.retire = retire ? 1u : 0u;
   P.pad_keep = b->keepalive_cap;
+  P.keys = (b->flags & WG_TIMERS_WIPE) ? (uint4*)c->keys : nullptr;
   hipLaunchKernelGGL(wgtm::k_tm_sweep_judge, dim3(ranges), dim3(256), 0, s, P);
   hipLaunchKernelGGL(wgrp::k_rx_scan, dim3(1), dim3(256), 0, s, P.part, ranges, (uint2*)(P.part + ranges));
   hipLaunchKernelGGL(wgtm::k_tm_sweep_place, dim3(std::max(ranges, rank_blocks(std::max(b->initiate_cap, b->keepalive_cap)))), dim3(256), 0, s, P, ranges);

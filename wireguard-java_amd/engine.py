@@ -389,8 +389,16 @@ class Engine:
         L.check(self._lib.wg_rx_sessions_count(self.ctx, ctypes.byref(live), ctypes.byref(retired)))
         return live.value, retired.value
 
+    def rx_sessions_compact(self, min_retired: int = 1, summary=None, stream: int | None = None) -> None:
+        """wg_rx_sessions_compact: if the session table holds at least max(min_retired, 1) retired entries it is
+        rebuilt on the device from its live ones (used == count afterwards); summary int32 [4] or None (live,
+        dropped, compacted, 0). Asynchronous and capturable. Needs rx_sessions_reserve()."""
+        L.check(self._lib.wg_rx_sessions_compact(self.ctx, min_retired, summary.data_ptr() if summary is not None else None,
+                                                 stream if stream is not None else _torch_stream()))
+
     def hs_install(self, entries, summary_n, send_slot, recv_slot, inst_status, summary, slot_first: int,
-                   slot_count: int, source: int, receivers=None, wipe: bool = True, stream: int | None = None) -> None:
+                   slot_count: int, source: int, receivers=None, wipe: bool = True, stream: int | None = None,
+                   compact: bool = False) -> None:
         """wg_hs_install over torch tensors: entries uint8 [n, 176] as hs_respond() wrote its sessions (source
         WG_HS_INSTALL_SESSIONS) or [n, 96] as hs_finish() wrote established (WG_HS_INSTALL_ESTABLISHED); summary_n
         that call's summary, int32 [4], whose n_ok is read on the device (None: all n entries); send_slot /
@@ -398,13 +406,15 @@ class Engine:
         inst_status int32 [n] (WG_HS_INST_*); summary int32 [4] (n_ok, n_badslot, n_dup, n_full); [slot_first,
         slot_first + slot_count) the key slots the call may write (seal1 / open1 / the queues refuse them
         afterwards); receivers the int32 table of set_receivers(), or None; wipe zeroes the installed entries'
-        keys. Needs rx_sessions_reserve(). The next tx_plan / rx_plan on the same stream uses the sessions."""
+        keys; compact rebuilds the session table from its live entries first when the ring would not fit beside the
+        retired ones (WG_HS_INSTALL_COMPACT). Needs rx_sessions_reserve(). The next tx_plan / rx_plan on the same
+        stream uses the sessions."""
         n_entries = summary_n.data_ptr() if summary_n is not None else None  # n_ok is the summaries' first word
         b = L.WgHsInstallBatch(entries.data_ptr(), n_entries, send_slot.data_ptr() if send_slot.shape[0] else None,
                                recv_slot.data_ptr() if recv_slot.shape[0] else None,
                                receivers.data_ptr() if receivers is not None else None, inst_status.data_ptr(),
                                summary.data_ptr(), entries.shape[0], send_slot.shape[0], slot_first, slot_count, source,
-                               L.WG_HS_INSTALL_WIPE if wipe else 0)
+                               (L.WG_HS_INSTALL_WIPE if wipe else 0) | (L.WG_HS_INSTALL_COMPACT if compact else 0))
         L.check(self._lib.wg_hs_install(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
 
     # ---- session timers (wg_timers_*) --------------------------------------------------------
@@ -459,26 +469,27 @@ class Engine:
         L.check(self._lib.wg_timers_mark(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
 
     def timers_sweep(self, now, expired, initiate, keepalives, summary, wire_stride: int = 0, out_size: int = 0,
-                     wire_base: int = 0, retire: bool = False, stream: int | None = None) -> None:
+                     wire_base: int = 0, retire: bool = False, stream: int | None = None, wipe: bool = False) -> None:
         """wg_timers_sweep over torch tensors: expired int32 [cap, 4] (send slot, recv slot, peer, local index),
         initiate int32 [cap] (hs_initiate()'s peer array, padded with -1), keepalives int64 [cap, 4] (wg_pkt records for
         seal(frame=True) into wire slots of wire_stride bytes of a ring of out_size bytes), summary int32 [8]
-        (expired due / listed, initiate due / listed, keepalives due / listed, live sessions, 0)."""
+        (expired due / listed, initiate due / listed, keepalives due / listed, live sessions, 0). wipe (with retire
+        only) zeroes both keys of every session the sweep retires (WG_TIMERS_WIPE)."""
         b = L.WgTimersSweepBatch(now.data_ptr(), expired.data_ptr() if expired.shape[0] else None,
                                  initiate.data_ptr() if initiate.shape[0] else None,
                                  keepalives.data_ptr() if keepalives.shape[0] else None, summary.data_ptr(), wire_base,
                                  wire_stride, out_size, expired.shape[0], initiate.shape[0], keepalives.shape[0],
-                                 L.WG_TIMERS_RETIRE if retire else 0)
+                                 (L.WG_TIMERS_RETIRE if retire else 0) | (L.WG_TIMERS_WIPE if wipe else 0))
         L.check(self._lib.wg_timers_sweep(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
 
     def timers_tick(self, now, expired, initiate, keepalives, summary, out, wire_stride: int, wire_base: int = 0,
-                    retire: bool = True, stream: int | None = None) -> None:
+                    retire: bool = True, stream: int | None = None, wipe: bool = False) -> None:
         """The tick on one stream, next to rx_open and tx_seal: timers_sweep, then the keepalives it listed are sealed
         and framed into `out` (the sweep pads the list with descriptors the seal skips: nothing is read back). The receiver table
         (set_receivers) must be set."""
         st = stream if stream is not None else _torch_stream()
         self.timers_sweep(now, expired, initiate, keepalives, summary, wire_stride=wire_stride, out_size=out.numel(),
-                          wire_base=wire_base, retire=retire, stream=st)
+                          wire_base=wire_base, retire=retire, stream=st, wipe=wipe)
         if keepalives.shape[0]:
             self.seal(keepalives, out, out, 16, stream=st, frame=True)
 
