@@ -816,6 +816,7 @@ int launch_after_seal(wg_ctx* c, const wg_batch* sb, const wg_batch* ob, hipStre
 #include "wg_plan.hip"
 #include "wg_rx.hip"
 #include "wg_tx.hip"
+#include "wg_session.hip"
 #include "wg_rxplan.hip"
 #include "wg_hs.hip"
 #include "wg_x25519.hip"

@@ -5,8 +5,8 @@
 // nothing moves it afterwards. WireGuard additionally moves a peer's endpoint to the source of every authenticated
 // packet. Here a peer's endpoint is one normalised 24-byte wg_hs_src of a per-peer table, a key slot's peer one word of
 // a per-key-slot map, and both sit at fixed device addresses:
-//   wg_endpoints_start  behind wg_hs_install: the installed sessions' slots -> peer, and the peer's endpoint from the
-//                       handshake datagram's source.
+//   wg_endpoints_start  behind wg_hs_install: the installed sessions' slots -> peer (wg_session.hip's `installed`), and
+//                       the peer's endpoint from the handshake datagram's source.
 //   wg_endpoints_learn  behind wg_rx_deliver: roaming; the last authenticated packet of a peer in the ring wins.
 //   wg_tx_sendlist      the transmit twin of wg_rx_deliver's items: {wire offset, length, destination} per sealed
 //                       datagram, and the gate that refuses a descriptor whose peer has no endpoint.
@@ -116,42 +116,19 @@ __device__ __forceinline__ void ep_item(wg_tx_item* it, uint64_t off, uint32_t l
 // ---- start ----
 struct EpStartParams {
   EpTables T;
-  const uint8_t* entries;
-  const uint32_t* n_entries;
+  InstView V;
   const uint32_t* status;
-  const uint32_t* send_slot;
-  const uint32_t* recv_slot;
   const wg_hs_src* src;
   uint32_t* claim;
   uint32_t* summary;
-  uint32_t n, n_slots, n_src, stride, w_pos, w_peer, learn;
+  uint32_t n_src, learn;
 };
-
-// entry j installed a session: its slots, its peer (WG_HS_NOPEER: none in the table) and its datagram's batch index
-__device__ __forceinline__ bool ep_start_entry(const EpStartParams& P, uint32_t j, uint32_t& s, uint32_t& r, uint32_t& peer,
-                                               uint32_t& index) {
-  if (j >= wgrp::dev_count(P.n_entries, P.n) || P.status[j] != WG_HS_INST_OK) return false;
-  const uint32_t* e = (const uint32_t*)(P.entries + (size_t)j * P.stride);
-  const uint32_t p = e[P.w_pos];
-  if (p >= P.n_slots) return false;
-  s = P.send_slot[p];
-  r = P.recv_slot[p];
-  if (s >= P.T.K || r >= P.T.K || s == r) return false;
-  peer = e[P.w_peer] < P.T.max_peers ? e[P.w_peer] : WG_HS_NOPEER;
-  index = e[0];  // (the first word of both entry formats)
-  return true;
-}
-
-__global__ void __launch_bounds__(256) k_ep_start_fill(EpStartParams P) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < P.T.max_peers) P.claim[i] = 0xFFFFFFFFu;
-}
 
 __global__ void __launch_bounds__(256) k_ep_start_map(EpStartParams P) {
   __shared__ uint32_t s_cnt[2][4];
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-  uint32_t s, r, peer = 0, index;
-  const bool ok = ep_start_entry(P, j, s, r, peer, index);
+  uint32_t s, r, peer = 0;
+  const bool ok = installed(P.V, P.status, P.T.K, P.T.max_peers, j, s, r, peer);
   if (ok) {
     P.T.map[s] = peer;
     P.T.map[r] = peer;
@@ -169,9 +146,10 @@ __global__ void __launch_bounds__(256) k_ep_start_map(EpStartParams P) {
 __global__ void __launch_bounds__(256) k_ep_start_write(EpStartParams P) {
   __shared__ uint32_t s_cnt[2][4];
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-  uint32_t s, r, peer, index;
+  uint32_t s, r, peer;
   bool learned = false, bad = false;
-  if (ep_start_entry(P, j, s, r, peer, index) && peer != WG_HS_NOPEER) {
+  if (installed(P.V, P.status, P.T.K, P.T.max_peers, j, s, r, peer) && peer != WG_HS_NOPEER) {
+    const uint32_t index = inst_entry(P.V, j)[0];  // the datagram's batch index: the first word of both entry formats
     EpAddr a;
     if (index < P.n_src && ep_norm(P.src + index, a)) {
       if (P.claim[peer] == j) {
@@ -234,16 +212,11 @@ __global__ void __launch_bounds__(256) k_ep_learn_claim(EpLearnParams P) {
     }
   }
   // Where every qualifying packet of a wave belongs to one peer (a ring from one peer), the wave's last qualifying
-  // lane, which holds its highest index, claims for all 64: one atomic per wave. One ballot decides; a wave with
-  // several peers claims per lane, as wg_timers_mark raises. A lane that finds the word past its index issues none.
+  // lane, which holds its highest index, claims for all 64: one atomic per wave. A lane that finds the word past its
+  // index issues none.
   {
-    const uint64_t act = __ballot(q);
-    bool mine = q;
-    if (act) {
-      const uint32_t l = 63u - (uint32_t)__clzll((unsigned long long)act);
-      const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int)p, (int)l);
-      if (!__ballot(q && p != k)) mine = (threadIdx.x & 63u) == l;
-    }
+    bool for_all;
+    const bool mine = wgrp::wave_elect<true>(q, p, for_all);
     if (mine && __hip_atomic_load(P.claim + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < i + 1u) (void)atomicMax(P.claim + p, i + 1u);
   }
   uint32_t r, n_q, n_bad;
@@ -442,11 +415,6 @@ __global__ void __launch_bounds__(256) k_ep_hs_place(EpHsSendParams P) {
   ep_item(P.items + pre.z + r, off, len, 0xFFFFFFFFu, peer, k, dst);
 }
 
-__global__ void __launch_bounds__(256) k_ep_map_init(uint32_t* map, uint32_t n) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n) map[i] = WG_HS_NOPEER;
-}
-
 }  // namespace wgep
 
 namespace {
@@ -484,7 +452,7 @@ int wg_endpoints_reserve(wg_ctx* c, uint32_t max_peers) {
     return rc;
   HIPTRY(t->order.create());
   HIPTRY(hipMemsetAsync(t->d_ep.p, 0, np * sizeof(wg_hs_src), c->stream));
-  hipLaunchKernelGGL(wgep::k_ep_map_init, dim3(rank_blocks(c->key_slots)), dim3(256), 0, c->stream, (uint32_t*)t->d_map.p, c->key_slots);
+  fill_u32(c->stream, t->d_map.p, c->key_slots, WG_HS_NOPEER);
   HIPTRY(hipGetLastError());
   HIPTRY(hipStreamSynchronize(c->stream));
   c->ep = t.release();
@@ -513,43 +481,27 @@ int wg_endpoints_get(wg_ctx* c, uint32_t first, uint32_t n, wg_hs_src* out) {
   if (!c || (!out && n)) return fail(WG_EINVAL, "NULL argument");
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  if (!c->ep) return fail(WG_EINVAL, "wg_endpoints_get before wg_endpoints_reserve");
-  if ((uint64_t)first + n > c->ep->max_peers) return fail(WG_ERANGE, "peers out of range");
-  if (!n) return WG_OK;
-  HIPTRY(hipDeviceSynchronize());
-  HIPTRY(hipMemcpy(out, (const wg_hs_src*)c->ep->d_ep.p + first, (size_t)n * sizeof(wg_hs_src), hipMemcpyDeviceToHost));
-  return WG_OK;
+  const EndpointsState* t = c->ep;
+  return range_copy(t ? t->d_ep.p : nullptr, "wg_endpoints_get before wg_endpoints_reserve", first, n, t ? t->max_peers : 0u, "peers", out, sizeof *out, true);
 }
 
 int wg_endpoint_slots_set(wg_ctx* c, uint32_t first, uint32_t n, const uint32_t* peers) {
   if (!c || (!peers && n)) return fail(WG_EINVAL, "NULL argument");
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  if (!c->ep) return fail(WG_EINVAL, "wg_endpoint_slots_set before wg_endpoints_reserve");
-  if ((uint64_t)first + n > c->key_slots) return fail(WG_ERANGE, "key slots out of range");
-  if (!n) return WG_OK;
-  HIPTRY(hipDeviceSynchronize());
-  HIPTRY(hipMemcpy((uint32_t*)c->ep->d_map.p + first, peers, (size_t)n * 4, hipMemcpyHostToDevice));
-  return WG_OK;
+  return range_copy(c->ep ? c->ep->d_map.p : nullptr, "wg_endpoint_slots_set before wg_endpoints_reserve", first, n, c->key_slots, "key slots", (void*)peers, 4, false);
 }
 
 int wg_endpoint_slots_get(wg_ctx* c, uint32_t first, uint32_t n, uint32_t* peers) {
   if (!c || (!peers && n)) return fail(WG_EINVAL, "NULL argument");
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  if (!c->ep) return fail(WG_EINVAL, "wg_endpoint_slots_get before wg_endpoints_reserve");
-  if ((uint64_t)first + n > c->key_slots) return fail(WG_ERANGE, "key slots out of range");
-  if (!n) return WG_OK;
-  HIPTRY(hipDeviceSynchronize());
-  HIPTRY(hipMemcpy(peers, (const uint32_t*)c->ep->d_map.p + first, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return WG_OK;
+  return range_copy(c->ep ? c->ep->d_map.p : nullptr, "wg_endpoint_slots_get before wg_endpoints_reserve", first, n, c->key_slots, "key slots", peers, 4, true);
 }
 
 int wg_endpoints_start(wg_ctx* c, const wg_endpoints_start_batch* b, void* stream) {
   if (!c || !b) return fail(WG_EINVAL, "NULL argument");
   if (b->_reserved) return fail(WG_EINVAL, "wg_endpoints_start_batch._reserved must be 0");
-  if (b->source != WG_HS_INSTALL_SESSIONS && b->source != WG_HS_INSTALL_ESTABLISHED)
-    return fail(WG_EINVAL, "unknown install source %u", b->source);
   if (b->flags & ~WG_EP_LEARN_RESPONSE) return fail(WG_EINVAL, "unknown endpoints start flags 0x%x", b->flags);
   if (!b->summary || (((uintptr_t)b->summary) & 7u)) return fail(WG_EINVAL, "summary must be non-NULL and 8-byte aligned");
   hipStream_t s = pick_stream(c, stream);
@@ -558,47 +510,34 @@ int wg_endpoints_start(wg_ctx* c, const wg_endpoints_start_batch* b, void* strea
   EndpointsState* t = c->ep;
   if (!t) return fail(WG_EINVAL, "wg_endpoints_start before wg_endpoints_reserve");
   const uint32_t n = b->n;
-  if (n > 0x40000000u) return fail(WG_E2BIG, "endpoints start of %u entries", n);
-  const bool sess = b->source == WG_HS_INSTALL_SESSIONS;
-  const bool learn = sess || (b->flags & WG_EP_LEARN_RESPONSE);
+  int rc;
+  if ((rc = inst_batch_check(*b, "endpoints start")) != WG_OK) return rc;
+  const InstView V = inst_view(*b);
+  const bool learn = b->source == WG_HS_INSTALL_SESSIONS || (b->flags & WG_EP_LEARN_RESPONSE);
   if (n) {
-    if (!b->entries || (((uintptr_t)b->entries) & 15u)) return fail(WG_EINVAL, "entries must be non-NULL and 16-byte aligned");
-    if (!b->inst_status || ((((uintptr_t)b->inst_status) | ((uintptr_t)b->n_entries)) & 3u))
-      return fail(WG_EINVAL, "inst_status must be non-NULL and 4-byte aligned (n_entries: 4-byte)");
-    if ((b->n_slots && (!b->send_slot || !b->recv_slot)) || ((((uintptr_t)b->send_slot) | ((uintptr_t)b->recv_slot)) & 3u))
-      return fail(WG_EINVAL, "send_slot / recv_slot must be non-NULL and 4-byte aligned");
+    if (!b->inst_status || (((uintptr_t)b->inst_status) & 3u)) return fail(WG_EINVAL, "inst_status must be non-NULL and 4-byte aligned");
     if ((b->n_src && !b->src) || (((uintptr_t)b->src) & 7u)) return fail(WG_EINVAL, "src must be non-NULL and 8-byte aligned");
-    const uint64_t stride = sess ? sizeof(wg_hs_session) : sizeof(wg_hs_established);
     const HsRange out[] = {{b->summary, sizeof(wg_endpoints_start_summary)}};
-    const HsRange in[] = {{b->entries, (uint64_t)n * stride}, {b->n_entries, b->n_entries ? 4u : 0u}, {b->inst_status, (uint64_t)n * 4},
+    const HsRange in[] = {{b->entries, (uint64_t)n * V.stride}, {b->n_entries, b->n_entries ? 4u : 0u}, {b->inst_status, (uint64_t)n * 4},
                           {b->send_slot, (uint64_t)b->n_slots * 4}, {b->recv_slot, (uint64_t)b->n_slots * 4},
                           {b->src, (uint64_t)b->n_src * sizeof(wg_hs_src)}};
     if (hs_ranges_overlap(out, in)) return fail(WG_EINVAL, "summary must not overlap an input of wg_endpoints_start");
   }
   const bool capturing = stream_capturing(s);
-  int rc;
   if ((rc = plan_begin(t->order, s, capturing, true, [] { return WG_OK; }, kEpStartWords, n)) != WG_OK) return rc;
   HIPTRY(hipMemsetAsync(b->summary, 0, sizeof(wg_endpoints_start_summary), s));
   if (n) {
     wgep::EpStartParams P{};
     P.T = ep_tables(c, t);
-    P.entries = (const uint8_t*)b->entries;
-    P.n_entries = b->n_entries;
+    P.V = V;
     P.status = b->inst_status;
-    P.send_slot = b->send_slot;
-    P.recv_slot = b->recv_slot;
     P.src = b->src;
     P.claim = (uint32_t*)t->d_claim.p;
     P.summary = (uint32_t*)b->summary;
-    P.n = n;
-    P.n_slots = b->n_slots;
     P.n_src = b->n_src;
-    P.stride = (uint32_t)(sess ? sizeof(wg_hs_session) : sizeof(wg_hs_established));
-    P.w_pos = (uint32_t)((sess ? offsetof(wg_hs_session, init) : offsetof(wg_hs_established, pending)) / 4);
-    P.w_peer = (uint32_t)((sess ? offsetof(wg_hs_session, peer) : offsetof(wg_hs_established, peer)) / 4);
     P.learn = learn ? 1u : 0u;
     const uint32_t nb = rank_blocks(n);
-    if (learn && t->max_peers) hipLaunchKernelGGL(wgep::k_ep_start_fill, dim3(rank_blocks(t->max_peers)), dim3(256), 0, s, P);
+    if (learn) fill_u32(s, P.claim, t->max_peers, 0xFFFFFFFFu);
     hipLaunchKernelGGL(wgep::k_ep_start_map, dim3(nb), dim3(256), 0, s, P);
     if (learn) hipLaunchKernelGGL(wgep::k_ep_start_write, dim3(nb), dim3(256), 0, s, P);
   }

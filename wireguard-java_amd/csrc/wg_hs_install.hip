@@ -11,7 +11,8 @@
 //
 // The key slots of an entry are the host's choice, made before the handshake chain is launched: send_slot[p],
 // recv_slot[p] with p = the position under which the host chose that handshake's local_index (sessions[j].init,
-// established[j].pending). Nothing is read back to pick them.
+// established[j].pending). Nothing is read back to pick them. The ring is read through wg_session.hip's InstView, as
+// wg_timers_start and wg_endpoints_start read it afterwards; the table's encoding and probe are that file's too.
 //
 // Five launches on the call's stream; a kernel boundary orders each behind the one before, no workgroup waits
 // for another, and which of several equal slots or indices wins (the lowest entry) depends on no dispatch order:
@@ -62,15 +63,11 @@ const PlanWords kHsInstWords{"handshake install", "entries", "wg_rx_sessions_res
 namespace wgin {
 
 struct InstParams {
-  uint8_t* entries;
-  const uint32_t* n_entries;
-  const uint32_t* send_slot;
-  const uint32_t* recv_slot;
+  InstView V;
   uint32_t* receivers;
   uint32_t* status;
   wg_hs_install_summary* summary;
-  uint32_t n, n_slots, slot_first, slot_count, key_slots, wipe;
-  uint32_t stride, w_pos, w_local, w_remote, q_keys;  // the entry's size, its fields as word / 16-B indices
+  uint32_t slot_first, slot_count, key_slots, wipe;
   RxSessHdr* hdr;
   uint32_t* claim;
   RxInstCtl* ctl;
@@ -80,9 +77,6 @@ struct InstParams {
   uint32_t words;                 // 64-bit words per window
 };
 
-__device__ __forceinline__ const uint32_t* inst_entry(const InstParams& P, uint32_t j) {
-  return (const uint32_t*)(P.entries + (size_t)j * P.stride);
-}
 __device__ __forceinline__ bool inst_slot_ok(const InstParams& P, uint32_t slot) {
   return slot >= P.slot_first && slot - P.slot_first < P.slot_count && slot < P.key_slots;
 }
@@ -98,70 +92,65 @@ __global__ void __launch_bounds__(256) k_inst_fill(InstParams P, uint32_t lo, ui
 
 __global__ void __launch_bounds__(256) k_inst_claim(InstParams P) {
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-  if (j >= wgrp::dev_count(P.n_entries, P.n)) return;
-  const uint32_t p = inst_entry(P, j)[P.w_pos];
-  bool ok = p < P.n_slots;
+  if (j >= inst_count(P.V)) return;
+  uint32_t s, r;
+  const bool ok = inst_slots(P.V, inst_entry(P.V, j), s, r) && inst_slot_ok(P, s) && inst_slot_ok(P, r) && s != r;
   if (ok) {
-    const uint32_t s = P.send_slot[p], r = P.recv_slot[p];
-    ok = inst_slot_ok(P, s) && inst_slot_ok(P, r) && s != r;
-    if (ok) {
-      (void)atomicMin(P.claim + s, j);
-      (void)atomicMin(P.claim + r, j);
-    }
+    (void)atomicMin(P.claim + s, j);
+    (void)atomicMin(P.claim + r, j);
   }
   P.status[j] = ok ? kInstPass1 : WG_HS_INST_BADSLOT;
 }
 
 __global__ void __launch_bounds__(256) k_inst_insert(InstParams P) {
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-  if (j >= wgrp::dev_count(P.n_entries, P.n) || P.status[j] != kInstPass1) return;
-  const uint32_t* e = inst_entry(P, j);
-  const uint32_t p = e[P.w_pos], index = e[P.w_local];
-  if (P.claim[P.send_slot[p]] != j || P.claim[P.recv_slot[p]] != j) {
+  if (j >= inst_count(P.V) || P.status[j] != kInstPass1) return;
+  const uint32_t* e = inst_entry(P.V, j);
+  const uint32_t index = e[P.V.w_local];
+  uint32_t s, r;
+  (void)inst_slots(P.V, e, s, r);  // (step 1 passed)
+  if (P.claim[s] != j || P.claim[r] != j) {
     P.status[j] = WG_HS_INST_DUPSLOT;
     return;
   }
   unsigned long long* ent = (unsigned long long*)P.hdr->entries;
-  const uint32_t mask = P.hdr->mask;
-  const unsigned long long mine = (unsigned long long)index | ((unsigned long long)(kRxTransient | j) << 32);
+  const unsigned long long mine = wgrp::u64_of(index, kRxTransient | j);
   uint32_t out = kInstOverflow;
-  uint32_t b = mix32(index);
-  for (uint32_t probes = 0; probes <= mask; ++probes, ++b) {  // every bucket once, at the most
-    unsigned long long* q = ent + (b & mask);
+  rx_probe(ent, P.hdr->mask, index, [&](unsigned long long* q) {
     unsigned long long v = inst_load(q);
-    if (!(uint32_t)(v >> 32)) {
+    if (rx_empty((uint32_t)(v >> 32))) {
       const unsigned long long old = atomicCAS(q, v, mine);
       if (old == v) {
-        out = kRxTransient | (b & mask);
-        break;
+        out = kRxTransient | (uint32_t)(q - ent);
+        return true;
       }
       v = old;  // another entry took the bucket: look at what it holds
     }
     const uint32_t h = (uint32_t)(v >> 32);
-    if ((uint32_t)v != index || h == kRxRetired) continue;
-    if (h & kRxTransient) {
+    if ((uint32_t)v != index || rx_retired(h)) return false;
+    if (rx_transient(h)) {
       (void)atomicMin(q, mine);
-      out = kRxTransient | (b & mask);
+      out = kRxTransient | (uint32_t)(q - ent);
     } else {
       out = WG_HS_INST_DUPINDEX;  // live at the call's start
     }
-    break;
-  }
+    return true;
+  });
   P.status[j] = out;
 }
 
 __global__ void __launch_bounds__(256) k_inst_count(InstParams P) {
   __shared__ uint32_t s_cnt[3][4];
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-  const bool in = j < wgrp::dev_count(P.n_entries, P.n);
+  const bool in = j < inst_count(P.V);
   uint32_t st = in ? P.status[j] : WG_HS_INST_OK;
   bool cand = false;
   if (in && st == kInstOverflow) {
-    const uint32_t index = inst_entry(P, j)[P.w_local];
+    const uint32_t index = inst_entry(P.V, j)[P.V.w_local];
     cand = true;
     for (uint32_t k = 0; k < j && cand; ++k) {
       const uint32_t sk = P.status[k];  // (entry k may be turning Overflow into OverflowDup: either says the same here)
-      if ((sk == kInstOverflow || sk == kInstOverflowDup) && inst_entry(P, k)[P.w_local] == index) cand = false;
+      if ((sk == kInstOverflow || sk == kInstOverflowDup) && inst_entry(P.V, k)[P.V.w_local] == index) cand = false;
     }
     if (!cand) P.status[j] = st = kInstOverflowDup;
   } else if (in && (st & kRxTransient)) {
@@ -197,7 +186,7 @@ __global__ void __launch_bounds__(256) k_inst_commit(InstParams P) {
       P.hdr->count += C.n_cand;
     }
   }
-  if (j >= wgrp::dev_count(P.n_entries, P.n)) return;
+  if (j >= inst_count(P.V)) return;
   if (tid == 0) s_st = P.status[j];
   __syncthreads();
   const uint32_t st = s_st;
@@ -214,17 +203,18 @@ __global__ void __launch_bounds__(256) k_inst_commit(InstParams P) {
     }
     return;
   }
-  const uint32_t* e = inst_entry(P, j);
-  const uint32_t p = e[P.w_pos], index = e[P.w_local], remote = e[P.w_remote];
-  const uint32_t s = P.send_slot[p], r = P.recv_slot[p];
+  const uint32_t* e = inst_entry(P.V, j);
+  const uint32_t index = e[P.V.w_local], remote = e[P.V.w_remote];
+  uint32_t s, r;
+  (void)inst_slots(P.V, e, s, r);  // (step 1 passed)
   if (tid < 4u) {  // send_key, recv_key: 4 x 16 B, each lane its own
-    uint4* k4 = (uint4*)(P.entries + (size_t)j * P.stride) + P.q_keys + tid;
+    uint4* k4 = (uint4*)e + P.V.q_keys + tid;
     const uint4 v = *k4;
     P.keys[2u * (tid < 2u ? s : r) + (tid & 1u)] = v;
     if (P.wipe) *k4 = make_uint4(0u, 0u, 0u, 0u);
   }
   if (tid == 0) {
-    *q = (unsigned long long)index | ((unsigned long long)(r + 1u) << 32);
+    *q = wgrp::u64_of(index, r + 1u);
     if (P.receivers) P.receivers[s] = remote;
     if (P.send) P.send[s] = P.send[r] = 0ull;
     if (P.top) P.top[s] = P.top[r] = 0ull;
@@ -248,27 +238,21 @@ extern "C" {
 int wg_hs_install(wg_ctx* c, const wg_hs_install_batch* b, void* stream) {
   if (!c || !b) return fail(WG_EINVAL, "NULL argument");
   if (b->flags & ~(WG_HS_INSTALL_WIPE | WG_HS_INSTALL_COMPACT)) return fail(WG_EINVAL, "unknown install flags 0x%x", b->flags);
-  if (b->source != WG_HS_INSTALL_SESSIONS && b->source != WG_HS_INSTALL_ESTABLISHED)
-    return fail(WG_EINVAL, "unknown install source %u", b->source);
-  if (((uintptr_t)b->n_entries) & 3u) return fail(WG_EINVAL, "n_entries must be 4-byte aligned");
+  if (((uintptr_t)b->n_entries) & 3u) return fail(WG_EINVAL, "n_entries must be 4-byte aligned");  // (of an empty ring too)
   hipStream_t s = pick_stream(c, stream);
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
   RxPlanState* t = c->rxp;
   if (!t || !t->reserved) return fail(WG_EINVAL, "wg_hs_install before wg_rx_sessions_reserve");
   const uint32_t n = b->n;
-  if (n == 0) return WG_OK;
-  if (n > 0x40000000u) return fail(WG_E2BIG, "handshake install of %u entries", n);
-  const bool sess = b->source == WG_HS_INSTALL_SESSIONS;
-  const uint64_t stride = sess ? sizeof(wg_hs_session) : sizeof(wg_hs_established);
-  if (!b->entries || (((uintptr_t)b->entries) & 15u)) return fail(WG_EINVAL, "entries must be non-NULL and 16-byte aligned");
-  if ((b->n_slots && (!b->send_slot || !b->recv_slot)) || ((((uintptr_t)b->send_slot) | ((uintptr_t)b->recv_slot)) & 3u))
-    return fail(WG_EINVAL, "send_slot / recv_slot must be non-NULL and 4-byte aligned");
+  int rc;
+  if ((rc = inst_batch_check(*b, "handshake install")) != WG_OK || n == 0) return rc;
+  const InstView V = inst_view(*b);
   if (!b->inst_status || (((uintptr_t)b->inst_status) & 3u) || !b->summary || (((uintptr_t)b->summary) & 7u) ||
       (((uintptr_t)b->receivers) & 3u))
     return fail(WG_EINVAL, "inst_status / summary must be non-NULL and aligned (4 / 8 bytes; receivers: 4)");
   {
-    const HsRange out[4] = {{b->entries, stride * n},
+    const HsRange out[4] = {{b->entries, (uint64_t)V.stride * n},
                             {b->inst_status, 4ull * n},
                             {b->summary, sizeof(wg_hs_install_summary)},
                             {b->receivers, b->receivers ? 4ull * c->key_slots : 0u}};
@@ -280,7 +264,6 @@ int wg_hs_install(wg_ctx* c, const wg_hs_install_batch* b, void* stream) {
   const bool capturing = stream_capturing(s);
   RxState* r = c->rx && c->rx->window ? c->rx : nullptr;
   TxState* x = c->tx;
-  int rc;
   if ((rc = plan_begin(t->order, s, capturing, true, [] { return WG_OK; }, kHsInstWords, n)) != WG_OK) return rc;
   if (!capturing && r && (rc = r->order.after_last(s)) != WG_OK) return rc;
   if (!capturing && x && (rc = x->order.after_last(s)) != WG_OK) return rc;
@@ -292,24 +275,14 @@ int wg_hs_install(wg_ctx* c, const wg_hs_install_batch* b, void* stream) {
     key_mirror_write(c, lo, hi - lo, nullptr);
   }
   wgin::InstParams P{};
-  P.entries = (uint8_t*)b->entries;
-  P.n_entries = b->n_entries;
-  P.send_slot = b->send_slot;
-  P.recv_slot = b->recv_slot;
+  P.V = V;
   P.receivers = b->receivers;
   P.status = b->inst_status;
   P.summary = b->summary;
-  P.n = n;
-  P.n_slots = b->n_slots;
   P.slot_first = b->slot_first;
   P.slot_count = b->slot_count;
   P.key_slots = c->key_slots;
   P.wipe = (b->flags & WG_HS_INSTALL_WIPE) ? 1u : 0u;
-  P.stride = (uint32_t)stride;
-  P.w_pos = (uint32_t)((sess ? offsetof(wg_hs_session, init) : offsetof(wg_hs_established, pending)) / 4);
-  P.w_local = (uint32_t)((sess ? offsetof(wg_hs_session, local_index) : offsetof(wg_hs_established, local_index)) / 4);
-  P.w_remote = (uint32_t)((sess ? offsetof(wg_hs_session, remote_index) : offsetof(wg_hs_established, remote_index)) / 4);
-  P.q_keys = (uint32_t)((sess ? offsetof(wg_hs_session, send_key) : offsetof(wg_hs_established, send_key)) / 16);
   P.hdr = (RxSessHdr*)t->d_hdr.p;
   P.claim = (uint32_t*)t->d_claim.p;
   P.ctl = (RxInstCtl*)t->d_ctl.p;

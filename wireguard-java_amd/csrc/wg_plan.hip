@@ -16,6 +16,9 @@
 // Ranks. A stable compaction over a batch is three launches on the call's stream (rank_launch): a first
 // kernel leaves one 16-B record of counts per range of kRankRange items, k_rx_scan turns the records into
 // their exclusive prefixes and writes the totals as the call's summary, a last kernel places.
+//
+// Small parts the session layer's calls share (wg_session.hip has the larger ones): k_fill_u32 / fill_u32,
+// wave_elect beside block_rank, and range_copy, the body of the per-slot and per-peer getters and setters.
 #pragma once
 
 namespace {
@@ -140,6 +143,22 @@ __device__ __forceinline__ void block_rank(bool flag, uint32_t* wsum, uint32_t& 
   }
 }
 
+// One atomic per wave where a wave's active lanes agree. Whether this lane should act on its `key`: if every active
+// lane holds one key, only the first (LAST: the last) active lane, and `for_all` says that it acts for all of them;
+// otherwise every active lane for itself. One ballot decides. Every lane of the wave must reach the call. (A round
+// per distinct key was measured and dropped: 64 dependent round trips per wave on a spread batch, docs/EXPERIMENTS.md.)
+template <bool LAST>
+__device__ __forceinline__ bool wave_elect(bool active, uint32_t key, bool& for_all) {
+  const uint64_t act = __ballot(active);
+  for_all = false;
+  if (!act) return false;
+  const uint32_t l = LAST ? 63u - (uint32_t)__clzll((unsigned long long)act) : (uint32_t)__ffsll((unsigned long long)act) - 1u;
+  const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int)key, (int)l);
+  if (__ballot(active && key != k)) return active;
+  for_all = true;
+  return (threadIdx.x & 63u) == l;
+}
+
 // The same for a 64-bit value: the sum of v over the threads below me (excl) and over all (total).
 __device__ __forceinline__ void block_scan64(uint64_t v, uint64_t* wsum, uint64_t& excl, uint64_t& total) {
   const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
@@ -159,6 +178,11 @@ __device__ __forceinline__ void block_scan64(uint64_t v, uint64_t* wsum, uint64_
     excl += k < w ? x : 0ull;
     total += x;
   }
+}
+
+__global__ void __launch_bounds__(256) k_fill_u32(uint32_t* p, uint32_t n, uint32_t value) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i < n) p[i] = value;
 }
 
 // Exclusive prefixes of the per-range records, in place, and the totals as the 16-B summary
@@ -193,6 +217,25 @@ __global__ void __launch_bounds__(256) k_rx_scan(uint4* part, uint32_t nb, uint2
 }  // namespace wgrp
 
 namespace {
+
+// p[0 .. n) = value on stream s: a claim array before its atomicMin, a map before its first entry
+void fill_u32(hipStream_t s, void* p, uint32_t n, uint32_t value) {
+  if (n) hipLaunchKernelGGL(wgrp::k_fill_u32, dim3(rank_blocks(n)), dim3(256), 0, s, (uint32_t*)p, n, value);
+}
+
+// Elements [first, first + n) of a state's device table `dev` (NULL: the state does not exist, and `unreserved` says
+// which call creates it) of `limit` elements of `elem` bytes, to the host or from it, behind everything queued on any
+// stream. The caller holds the context's lock and device.
+int range_copy(void* dev, const char* unreserved, uint32_t first, uint32_t n, uint32_t limit, const char* units, void* host, size_t elem,
+               bool to_host) {
+  if (!dev) return fail(WG_EINVAL, "%s", unreserved);
+  if ((uint64_t)first + n > limit) return fail(WG_ERANGE, "%s out of range", units);
+  if (!n) return WG_OK;
+  HIPTRY(hipDeviceSynchronize());
+  uint8_t* d = (uint8_t*)dev + (size_t)first * elem;
+  HIPTRY(hipMemcpy(to_host ? host : d, to_host ? d : host, (size_t)n * elem, to_host ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice));
+  return WG_OK;
+}
 
 // A rank over P.n items: `first` (one record per range to P.part), k_rx_scan (prefixes, and the totals as
 // the 16-B `summary`), `last`; no workgroup waits on another.

@@ -17,7 +17,8 @@
 // reference's indices are 0, 1, 2, ..., WireGuard's are random, a test's may be multiples of anything: the
 // finaliser spreads them all), linear probing; at most a quarter full, so a probe sequence is short (a
 // wave walks as long as the longest of its 64) and ends at an empty entry. Its header sits at a fixed
-// device address and names the entries (wg_plan.hip, fixed headers).
+// device address and names the entries (wg_plan.hip, fixed headers). The entry's encoding, its predicates and the
+// probe that every walker but the plan's own lookup uses are wg_session.hip's.
 //
 // A table the device can change. wg_rx_sessions_reserve gives the table a fixed capacity C of the context's
 // own entries; wg_hs_install (wg_hs_install.hip) then inserts into it and wg_rx_sessions_retire turns a live
@@ -61,17 +62,6 @@
 #pragma once
 
 namespace {
-
-constexpr uint32_t kRxRetired = 0xFFFFFFFFu;    // high word of a retired entry (no key slot is 0xFFFFFFFE)
-constexpr uint32_t kRxTransient = 0x80000000u;  // high word 0x80000000 | j: entry j of a running wg_hs_install
-
-struct RxSessHdr {  // at a fixed device address; a table change rewrites it (and may move the entries)
-  const uint2* entries;  // capacity x {index, key slot + 1 (0: empty, kRxRetired: retired)}
-  uint32_t mask;         // capacity - 1; bucket = mix32(index) & mask
-  uint32_t count;        // live entries
-  uint32_t used;         // live + retired entries
-  uint32_t _pad;
-};
 
 struct RxInstCtl {  // wg_hs_install's words between its launches (written by its first launch in every call)
   uint32_t used0, n_cand, n_badslot, n_dup;
@@ -165,12 +155,15 @@ int rxp_table_set(wg_ctx* c, RxPlanState* t, const uint32_t* indices, const uint
   std::vector<uint2> ent(own ? (size_t)H.mask + 1 : 0, make_uint2(0u, 0u));
   for (uint32_t k = 0; k < n; ++k) {
     if (slots[k] >= c->key_slots) return fail(WG_ERANGE, "session %u: key slot %u >= %u", k, slots[k], c->key_slots);
-    uint32_t b = mix32(indices[k]) & H.mask;
-    while (ent[b].y) {
-      if (ent[b].x == indices[k]) return fail(WG_EINVAL, "session %u: receiver index 0x%08x repeats", k, indices[k]);
-      b = (b + 1u) & H.mask;
-    }
-    ent[b] = make_uint2(indices[k], slots[k] + 1u);
+    bool placed = false;  // (n entries in >= 4 n buckets: the walk ends at an empty one)
+    rx_probe(ent.data(), H.mask, indices[k], [&](uint2* e) {
+      if (rx_empty(e->y)) {
+        *e = make_uint2(indices[k], slots[k] + 1u);
+        placed = true;
+      }
+      return placed || e->x == indices[k];
+    });
+    if (!placed) return fail(WG_EINVAL, "session %u: receiver index 0x%08x repeats", k, indices[k]);
   }
   int rc;
   HIPTRY(hipDeviceSynchronize());  // the entries may move: no plan launched earlier (on any stream) may still read them
@@ -243,37 +236,22 @@ __device__ __forceinline__ uint32_t rx_session(const RxSessHdr& H, uint32_t inde
   for (uint32_t probes = 0; probes <= H.mask; probes += 2u) {  // (a table at most half full ends the walk long before)
     const uint64_t e0 = ent[b & H.mask], e1 = ent[(b + 1u) & H.mask];
     const uint32_t h0 = (uint32_t)(e0 >> 32), h1 = (uint32_t)(e1 >> 32);
-    if (!h0) return 0u;
-    if ((uint32_t)e0 == index && h0 != kRxRetired) return h0;
-    if (!h1) return 0u;
-    if ((uint32_t)e1 == index && h1 != kRxRetired) return h1;
+    if (rx_empty(h0)) return 0u;
+    if ((uint32_t)e0 == index && !rx_retired(h0)) return h0;
+    if (rx_empty(h1)) return 0u;
+    if ((uint32_t)e1 == index && !rx_retired(h1)) return h1;
     b += 2u;
   }
   return 0u;
 }
 
-// One index per thread: a live entry becomes a retired one by a 64-bit CAS, so of equal indices in one call
-// exactly one thread retires it (and counts it).
+// One index per thread; of equal indices in one call exactly one thread retires the entry (and counts it).
 __global__ void __launch_bounds__(256) k_rx_retire(RxSessHdr* hdr, const uint32_t* indices, uint32_t n, uint32_t* n_retired) {
   __shared__ uint32_t s_cnt[4];
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   const RxSessHdr H = *hdr;
   bool mine = false;
-  if (i < n) {
-    const uint32_t index = indices[i];
-    unsigned long long* ent = (unsigned long long*)H.entries;
-    uint32_t b = mix32(index);
-    for (uint32_t probes = 0; probes <= H.mask; ++probes, ++b) {
-      unsigned long long* e = ent + (b & H.mask);
-      const unsigned long long v = *e;
-      const uint32_t h = (uint32_t)(v >> 32);
-      if (!h) break;
-      if ((uint32_t)v == index && h != kRxRetired) {  // the one live entry of this index
-        mine = atomicCAS(e, v, (unsigned long long)index | ((unsigned long long)kRxRetired << 32)) == v;
-        break;
-      }
-    }
-  }
+  if (i < n) mine = rx_retire_entry(H, indices[i], 0u);
   uint32_t r, total;
   block_rank(mine, s_cnt, r, total);
   if (threadIdx.x == 0 && total) {
@@ -314,9 +292,8 @@ __global__ void __launch_bounds__(256) k_rx_compact_clear(RxCompactParams P) {
   }
 }
 
-// One bucket of the current table per thread. Live: a high word that is neither 0 nor retired nor transient (between
-// calls there are no transient entries). The walk is bounded by the capacity; the spare holds at most `count` <= C / 2
-// entries, so it ends long before.
+// One bucket of the current table per thread. The walk is bounded by the capacity; the spare holds at most
+// `count` <= C / 2 entries, so it ends long before.
 __global__ void __launch_bounds__(256) k_rx_compact_rehash(RxCompactParams P) {
   if (!P.ctl->go) return;
   const RxSessHdr H = *P.hdr;
@@ -324,11 +301,8 @@ __global__ void __launch_bounds__(256) k_rx_compact_rehash(RxCompactParams P) {
   unsigned long long* spare = (unsigned long long*)rx_spare(P, H.entries);
   for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i <= H.mask; i += (uint64_t)gridDim.x * 256u) {
     const unsigned long long v = cur[i];
-    const uint32_t h = (uint32_t)(v >> 32);
-    if (!h || (h & kRxTransient)) continue;  // (kRxRetired has the transient bit)
-    uint32_t b = mix32((uint32_t)v);
-    for (uint32_t probes = 0; probes <= H.mask; ++probes, ++b)
-      if (atomicCAS(spare + (b & H.mask), 0ull, v) == 0ull) break;
+    if (!rx_live((uint32_t)(v >> 32))) continue;
+    rx_probe(spare, H.mask, (uint32_t)v, [v](unsigned long long* e) { return atomicCAS(e, 0ull, v) == 0ull; });
   }
 }
 
@@ -539,7 +513,7 @@ int wg_rx_sessions_reserve(wg_ctx* c, uint32_t max_sessions) {
   if (!old.empty()) HIPTRY(hipMemcpy(old.data(), H.entries, old.size() * sizeof(uint2), hipMemcpyDeviceToHost));
   std::vector<uint32_t> indices, slots;
   for (const uint2& e : old)
-    if (e.y && e.y != kRxRetired) {
+    if (rx_live(e.y)) {
       indices.push_back(e.x);
       slots.push_back(e.y - 1u);
     }

@@ -7,7 +7,8 @@
 // (KeepaliveSender.java:29-85: one as soon as the session changes, :69-73, then one per interval). Here a session
 // is two records of a per-key-slot table, a peer one record of a per-peer table, and time a tick count the host
 // writes into device memory:
-//   wg_timers_start  behind wg_hs_install: the records of the sessions it installed; the peer's current session.
+//   wg_timers_start  behind wg_hs_install: the records of the sessions it installed (wg_session.hip's `installed`);
+//                    the peer's current session.
 //   wg_timers_mark   behind wg_rx_deliver / wg_tx_plan: proof of life per key slot, and the gate that refuses a
 //                    descriptor on a session that is dead or past its limits.
 //   wg_timers_sweep  the tick: the expired sessions (their retirement, and with WIPE their keys zeroed), the peers to initiate to in
@@ -83,50 +84,32 @@ __device__ __forceinline__ void tm_raise(uint64_t* p, uint64_t now) {
 // ---- start ----
 struct TmStartParams {
   TmTables T;
-  const uint8_t* entries;
-  const uint32_t* n_entries;
+  InstView V;
   const uint32_t* status;
-  const uint32_t* send_slot;
-  const uint32_t* recv_slot;
   uint32_t* claim;
-  uint32_t n, n_slots, stride, w_pos, w_peer, w_local, role;
+  uint32_t role;
 };
 
-// entry j starts a session: its slots, its peer (WG_HS_NOPEER: none in the table) and its index
-__device__ __forceinline__ bool tm_start_entry(const TmStartParams& P, uint32_t j, uint32_t& s, uint32_t& r, uint32_t& peer,
-                                               uint32_t& index) {
-  if (j >= wgrp::dev_count(P.n_entries, P.n) || P.status[j] != WG_HS_INST_OK) return false;
-  const uint32_t* e = (const uint32_t*)(P.entries + (size_t)j * P.stride);
-  const uint32_t p = e[P.w_pos];
-  if (p >= P.n_slots) return false;
-  s = P.send_slot[p];
-  r = P.recv_slot[p];
-  if (s >= P.T.K || r >= P.T.K || s == r) return false;
-  peer = e[P.w_peer] < P.T.max_peers ? e[P.w_peer] : WG_HS_NOPEER;
-  index = e[P.w_local];
-  return true;
+// a session ends: both its records are dead, and its peer has no current session if it was that. (Writers of one
+// word all write the same value.)
+__device__ __forceinline__ void tm_end(const TmTables& T, uint32_t send_slot, uint32_t recv_slot, uint32_t peer) {
+  if (send_slot < T.K) T.slots[send_slot].state = WG_TIMER_DEAD;
+  if (recv_slot < T.K) T.slots[recv_slot].state = WG_TIMER_DEAD;
+  if (peer < T.max_peers && T.peers[peer].current == send_slot) T.peers[peer].current = WG_TIMER_NOSLOT;
 }
 
-// the live session that owns `slot` dies: its other record, and its peer's current if it is that. (Writers of one
-// word all write the same value.)
+// the live session that owns `slot` ends (a start takes the slot)
 __device__ __forceinline__ void tm_kill(const TmTables& T, uint32_t slot) {
   const uint4 h = *(const uint4*)(T.slots + slot);  // state, peer, local_index, partner
   if (!tm_live(h.x)) return;
-  const uint32_t q = h.w;
-  if (q < T.K) T.slots[q].state = WG_TIMER_DEAD;
-  const uint32_t snd = tm_send(h.x) ? slot : q;
-  if (h.y < T.max_peers && T.peers[h.y].current == snd) T.peers[h.y].current = WG_TIMER_NOSLOT;
-}
-
-__global__ void __launch_bounds__(256) k_tm_start_fill(TmStartParams P) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < P.T.max_peers) P.claim[i] = 0xFFFFFFFFu;
+  const bool snd = tm_send(h.x);
+  tm_end(T, snd ? slot : h.w, snd ? h.w : slot, h.y);
 }
 
 __global__ void __launch_bounds__(256) k_tm_start_kill(TmStartParams P) {
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-  uint32_t s, r, peer, index;
-  if (*P.T.now == 0ull || !tm_start_entry(P, j, s, r, peer, index)) return;
+  uint32_t s, r, peer;
+  if (*P.T.now == 0ull || !installed(P.V, P.status, P.T.K, P.T.max_peers, j, s, r, peer)) return;
   tm_kill(P.T, s);
   tm_kill(P.T, r);
   if (peer != WG_HS_NOPEER) (void)atomicMin(P.claim + peer, j);
@@ -135,8 +118,9 @@ __global__ void __launch_bounds__(256) k_tm_start_kill(TmStartParams P) {
 __global__ void __launch_bounds__(256) k_tm_start_write(TmStartParams P) {
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
   const uint64_t now = *P.T.now;
-  uint32_t s, r, peer, index;
-  if (now == 0ull || !tm_start_entry(P, j, s, r, peer, index)) return;
+  uint32_t s, r, peer;
+  if (now == 0ull || !installed(P.V, P.status, P.T.K, P.T.max_peers, j, s, r, peer)) return;
+  const uint32_t index = inst_entry(P.V, j)[P.V.w_local];
   const bool win = peer != WG_HS_NOPEER && P.claim[peer] == j;
   const uint64_t sup = (peer != WG_HS_NOPEER && !win) ? now : 0ull;
   const uint32_t n_lo = (uint32_t)now, n_hi = (uint32_t)(now >> 32);
@@ -197,23 +181,14 @@ __global__ void __launch_bounds__(256) k_tm_mark(TmMarkParams P) {
     }
   }
   // Where every mark of a wave names one slot (a batch on one session), the wave's first marking lane raises for all
-  // 64: one atomic per wave and stamp. One ballot decides; a wave with several slots raises per lane. (A round per
-  // distinct slot was measured and dropped: 64 dependent round trips per wave on a spread batch, docs/EXPERIMENTS.md.)
+  // 64, last_data if any of them carried data: one atomic per wave and stamp.
   {
-    const uint64_t act = __ballot(marked);
-    bool mine = marked, mine_data = data;
-    if (act) {
-      const uint32_t l = (uint32_t)__ffsll((unsigned long long)act) - 1u;
-      const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int)slot, (int)l);
-      const uint64_t any_data = __ballot(marked && data);
-      if (!__ballot(marked && slot != k)) {
-        mine = (threadIdx.x & 63u) == l;
-        mine_data = any_data != 0ull;
-      }
-    }
+    bool for_all;
+    const bool mine = wgrp::wave_elect<false>(marked, slot, for_all);
+    const uint64_t any_data = __ballot(marked && data);
     if (mine) {
       tm_raise(&P.T.slots[slot].last, now);
-      if (mine_data) tm_raise(&P.T.slots[slot].last_data, now);
+      if (for_all ? any_data != 0ull : data) tm_raise(&P.T.slots[slot].last_data, now);
     }
   }
   uint32_t r, n_marked, n_refused;
@@ -313,25 +288,9 @@ __global__ void __launch_bounds__(256) k_tm_sweep_place(TmSweepParams P, uint32_
     const uint4 h = *(const uint4*)(T.slots + g);  // state, peer, local_index, partner
     *(uint4*)(P.expired + pre.x + re) = make_uint4(g, h.w, h.y, h.z);
     if (P.retire) {
-      if (P.hdr) {  // as k_rx_retire: the one live entry of this index becomes a retired one
-        const RxSessHdr H = *P.hdr;
-        unsigned long long* ent = (unsigned long long*)H.entries;
-        uint32_t b = mix32(h.z);
-        for (uint32_t probes = 0; probes <= H.mask; ++probes, ++b) {
-          unsigned long long* e = ent + (b & H.mask);
-          const unsigned long long v = *e;
-          const uint32_t hi = (uint32_t)(v >> 32);
-          if (!hi) break;
-          if ((uint32_t)v == h.z && hi != kRxRetired && !(hi & kRxTransient)) {
-            // (only if it still names this session's recv slot: the index may have been installed again)
-            if (hi == h.w + 1u) retired = atomicCAS(e, v, (unsigned long long)h.z | ((unsigned long long)kRxRetired << 32)) == v;
-            break;
-          }
-        }
-      }
-      T.slots[g].state = WG_TIMER_DEAD;
-      if (h.w < T.K) T.slots[h.w].state = WG_TIMER_DEAD;
-      if (h.y < T.max_peers && T.peers[h.y].current == g) T.peers[h.y].current = WG_TIMER_NOSLOT;
+      // (the index's entry only if it still names this session's recv slot: the index may have been installed again)
+      if (P.hdr) retired = rx_retire_entry(*P.hdr, h.z, h.w + 1u);
+      tm_end(T, g, h.w, h.y);
       if (P.keys) {  // the session's two keys: stores of zero, no key byte is loaded
         const uint4 z = make_uint4(0u, 0u, 0u, 0u);
         P.keys[2u * g] = z;
@@ -469,31 +428,21 @@ int wg_timers_get(wg_ctx* c, uint32_t first, uint32_t n, wg_timer_slot* out) {
   if (!c || (!out && n)) return fail(WG_EINVAL, "NULL argument");
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  if (!c->tm) return fail(WG_EINVAL, "wg_timers_get before wg_timers_reserve");
-  if ((uint64_t)first + n > c->key_slots) return fail(WG_ERANGE, "key slots out of range");
-  if (!n) return WG_OK;
-  HIPTRY(hipDeviceSynchronize());
-  HIPTRY(hipMemcpy(out, (const wg_timer_slot*)c->tm->d_slots.p + first, (size_t)n * sizeof(wg_timer_slot), hipMemcpyDeviceToHost));
-  return WG_OK;
+  const TimersState* t = c->tm;
+  return range_copy(t ? t->d_slots.p : nullptr, "wg_timers_get before wg_timers_reserve", first, n, c->key_slots, "key slots", out, sizeof *out, true);
 }
 
 int wg_timers_peers_get(wg_ctx* c, uint32_t first, uint32_t n, wg_timer_peer_state* out) {
   if (!c || (!out && n)) return fail(WG_EINVAL, "NULL argument");
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  if (!c->tm) return fail(WG_EINVAL, "wg_timers_peers_get before wg_timers_reserve");
-  if ((uint64_t)first + n > c->tm->max_peers) return fail(WG_ERANGE, "peers out of range");
-  if (!n) return WG_OK;
-  HIPTRY(hipDeviceSynchronize());
-  HIPTRY(hipMemcpy(out, (const wg_timer_peer_state*)c->tm->d_peers.p + first, (size_t)n * sizeof(wg_timer_peer_state), hipMemcpyDeviceToHost));
-  return WG_OK;
+  const TimersState* t = c->tm;
+  return range_copy(t ? t->d_peers.p : nullptr, "wg_timers_peers_get before wg_timers_reserve", first, n, t ? t->max_peers : 0u, "peers", out, sizeof *out, true);
 }
 
 int wg_timers_start(wg_ctx* c, const wg_timers_start_batch* b, void* stream) {
   if (!c || !b) return fail(WG_EINVAL, "NULL argument");
   if (b->_reserved) return fail(WG_EINVAL, "wg_timers_start_batch._reserved must be 0");
-  if (b->source != WG_HS_INSTALL_SESSIONS && b->source != WG_HS_INSTALL_ESTABLISHED)
-    return fail(WG_EINVAL, "unknown install source %u", b->source);
   if (!b->now || (((uintptr_t)b->now) & 7u)) return fail(WG_EINVAL, "now must be non-NULL and 8-byte aligned");
   hipStream_t s = pick_stream(c, stream);
   std::lock_guard<std::mutex> lk(c->mu);
@@ -501,34 +450,19 @@ int wg_timers_start(wg_ctx* c, const wg_timers_start_batch* b, void* stream) {
   TimersState* t = c->tm;
   if (!t) return fail(WG_EINVAL, "wg_timers_start before wg_timers_reserve");
   const uint32_t n = b->n;
-  if (n == 0) return WG_OK;
-  if (n > 0x40000000u) return fail(WG_E2BIG, "timers start of %u entries", n);
-  if (!b->entries || (((uintptr_t)b->entries) & 15u)) return fail(WG_EINVAL, "entries must be non-NULL and 16-byte aligned");
-  if (!b->inst_status || ((((uintptr_t)b->inst_status) | ((uintptr_t)b->n_entries)) & 3u))
-    return fail(WG_EINVAL, "inst_status must be non-NULL and 4-byte aligned (n_entries: 4-byte)");
-  if ((b->n_slots && (!b->send_slot || !b->recv_slot)) || ((((uintptr_t)b->send_slot) | ((uintptr_t)b->recv_slot)) & 3u))
-    return fail(WG_EINVAL, "send_slot / recv_slot must be non-NULL and 4-byte aligned");
-  const bool capturing = stream_capturing(s);
   int rc;
+  if ((rc = inst_batch_check(*b, "timers start")) != WG_OK || n == 0) return rc;
+  if (!b->inst_status || (((uintptr_t)b->inst_status) & 3u)) return fail(WG_EINVAL, "inst_status must be non-NULL and 4-byte aligned");
+  const bool capturing = stream_capturing(s);
   if ((rc = plan_begin(t->order, s, capturing, true, [] { return WG_OK; }, kTmStartWords, n)) != WG_OK) return rc;
-  const bool sess = b->source == WG_HS_INSTALL_SESSIONS;
   wgtm::TmStartParams P{};
   P.T = tm_tables(c, t, b->now);
-  P.entries = (const uint8_t*)b->entries;
-  P.n_entries = b->n_entries;
+  P.V = inst_view(*b);
   P.status = b->inst_status;
-  P.send_slot = b->send_slot;
-  P.recv_slot = b->recv_slot;
   P.claim = (uint32_t*)t->d_claim.p;
-  P.n = n;
-  P.n_slots = b->n_slots;
-  P.stride = (uint32_t)(sess ? sizeof(wg_hs_session) : sizeof(wg_hs_established));
-  P.w_pos = (uint32_t)((sess ? offsetof(wg_hs_session, init) : offsetof(wg_hs_established, pending)) / 4);
-  P.w_peer = (uint32_t)((sess ? offsetof(wg_hs_session, peer) : offsetof(wg_hs_established, peer)) / 4);
-  P.w_local = (uint32_t)((sess ? offsetof(wg_hs_session, local_index) : offsetof(wg_hs_established, local_index)) / 4);
-  P.role = sess ? WG_TIMER_SEND_RESPONDER : WG_TIMER_SEND_INITIATOR;
+  P.role = b->source == WG_HS_INSTALL_SESSIONS ? WG_TIMER_SEND_RESPONDER : WG_TIMER_SEND_INITIATOR;
   const uint32_t nb = rank_blocks(n);
-  if (t->max_peers) hipLaunchKernelGGL(wgtm::k_tm_start_fill, dim3(rank_blocks(t->max_peers)), dim3(256), 0, s, P);
+  fill_u32(s, P.claim, t->max_peers, 0xFFFFFFFFu);
   hipLaunchKernelGGL(wgtm::k_tm_start_kill, dim3(nb), dim3(256), 0, s, P);
   hipLaunchKernelGGL(wgtm::k_tm_start_write, dim3(nb), dim3(256), 0, s, P);
   return plan_end(t->order, s, capturing, kTmStartWords);
