@@ -1171,10 +1171,11 @@ int wg_hs_stamps_get(wg_ctx* ctx, uint32_t first_peer, uint32_t n, uint8_t* stam
  *
  * For all of these calls, no branch, address or loop bound depends on the secret, a cookie, a cookie key, a subkey or
  *   a keystream byte; the one exception is the all-zero test of a raw nonce. Source addresses, indices, peer
- *   positions and the statuses (the comparisons' outcomes among them) are public. Not here: a rate limiter and the
- *   "under load" decision (the host chooses wg_hs_check or wg_hs_admit per ring), expiry and rotation (the host's
- *   clock, through the setters), mac2 inside wg_hs_respond's sessions (wg_hs_mac2 takes 92-byte records if the host
- *   copies them), and type 3 in wg_rx_plan's lists. */
+ *   positions and the statuses (the comparisons' outcomes among them) are public. Not here: the "under load"
+ *   decision (the host chooses wg_hs_check or wg_hs_admit per ring; the rate limiter that goes with it is
+ *   wg_hs_ratelimit, below), expiry and rotation (the host's clock, through the setters), mac2 inside
+ *   wg_hs_respond's sessions (wg_hs_mac2 takes 92-byte records if the host copies them), and type 3 in
+ *   wg_rx_plan's lists. */
 #define WG_HS_BADSRC 5u     /* wg_hs_admit: src.family is neither 4 nor 6 */
 #define WG_HS_NONONCE 6u    /* wg_hs_admit: a cookie is needed and the position's nonce is all zero */
 #define WG_HS_NEEDCOOKIE 7u /* wg_hs_admit: mac2 does not verify; a cookie reply was emitted */
@@ -1248,6 +1249,106 @@ int wg_hs_cookies_get(wg_ctx* ctx, uint32_t first_peer, uint32_t n, uint8_t* coo
 int wg_hs_cookies_set(wg_ctx* ctx, uint32_t first_peer, uint32_t n, const uint8_t* cookies_host /* 16 n */,
                       const uint8_t* have_host /* n */);
 int wg_hs_mac2(wg_ctx* ctx, const wg_hs_mac2_batch* batch, void* stream);
+
+/* ---- handshakes rate-limited per source, on the device ----
+ * wg_hs_admit stops a spoofed flood; a sender that owns its address completes one cookie round trip and then sends
+ * fresh initiations with a valid mac2, each of which costs a ladder and the open chain. WireGuard's second half of
+ * its under-load rule: a message with a valid cookie still has to pass a token bucket of its source before any curve
+ * work is spent (20 handshakes per second, a burst of 5, keyed by the IPv4 address or the IPv6 /64). The reference
+ * has no limiter; this is what the library ADDS, after wg_hs_stamp and wg_hs_admit, and no other call changes.
+ *
+ * The rule. A limiter is `cost` ticks per handshake and `burst` handshakes: max = burst * cost, 1 <= burst <=
+ *   WG_HS_RL_MAX_BURST, 1 <= cost <= 2^56. The key of a source is {family, addr[0 .. 4)} (family 4) or {family,
+ *   addr[0 .. 8)} (family 6): not the port, not the bytes of wg_hs_src.addr behind an IPv4 address, not the low 64
+ *   bits of an IPv6 address. An entry is {key, tokens, last}. One record at tick `now`:
+ *   1. the key has no entry: create {tokens = max, last = now}.  2. age = now >= last ? now - last : 0.
+ *   3. tokens = min(max, tokens + age) (the sum saturates).  4. last = now only if now >= last (a clock that steps
+ *   back ages nothing and moves nothing, like the session timers).  5. tokens >= cost: tokens -= cost, the record
+ *   passes; otherwise WG_HS_RL_LIMITED.
+ *   A call applies this to its records IN LIST ORDER, ALL AT ONE now, which has a closed form: a source with c records
+ *   in the call has the allowance a = min(max, tokens + age) / cost; its min(a, c) records with the LOWEST positions
+ *   pass, whatever the dispatch order, the others are LIMITED, and its entry ends as {refilled - min(a, c) * cost,
+ *   max(last, now)}. An entry with now - last >= max is indistinguishable from no entry, so dropping such entries
+ *   (the compaction below) only reclaims space WHILE THE CLOCK DOES NOT STEP BACK: after a step back a dropped
+ *   entry would have kept its `last`, and its source gets a full bucket earlier than the sequential rule gives it.
+ *
+ * wg_hs_rl_reserve(ctx, max_sources): an open-addressing table of C buckets, C the smallest power of two >= max(8, 2 *
+ *   max_sources), behind a header at a fixed device address, a second buffer of the same size for the compaction,
+ *   and per bucket the call's scratch (a count and WG_HS_RL_MAX_BURST words); the per-record scratch is sized with
+ *   wg_hs_reserve. The table never holds more than C / 2 entries. A smaller or equal max_sources later is a no-op,
+ *   a larger one rebuilds the table with its entries kept. max_sources above 2^27: WG_E2BIG. Synchronous.
+ * wg_hs_rl_config_set(ctx, cost, burst): synchronous and ordered after everything queued before it. Both values live
+ *   on the device: a new cost needs no re-capture. A call runs `burst` selection launches, fixed when it is queued or
+ *   captured: a captured call must be captured again after a GREATER burst (a smaller one replays correctly). Values
+ *   out of range: WG_EINVAL.
+ * wg_hs_ratelimit(ctx, b, stream): records are wg_hs_check's or wg_hs_admit's; n_records a device count
+ *   (&wg_hs_summary.n_valid) or NULL (all n); src is the ring's wg_hs_src[n_src] by BATCH INDEX; now a device tick
+ *   count (8-byte aligned). For every position k < min(*n_records, n), rl_status[k] is, in this order:
+ *   1. WG_HS_RL_BADSRC: records[k].index >= n_src, or the source's family is neither 4 nor 6.
+ *   2. WG_HS_RL_FULL: with U the entries of the table before the call and m the records of the call (records, not
+ *      distinct sources) whose key has no entry before the call, U + m > C / 2: each of those m records is FULL and the
+ *      call inserts nothing. Records of known sources are served as usual. (wg_hs_install's rule for a full table.)
+ *   3. WG_HS_RL_LIMITED, by the rule above.   4. WG_HS_RL_OK.
+ *   out_records[0 .. n_passed) is the stable compaction of the OK records, copied whole; nothing behind it is touched.
+ *   rl_summary = {n_passed, n_limited, n_full, n_badsrc}: its first word is what wg_hs_dh_batch.n_records takes next.
+ *   *now == 0 ("never", like the session timers): every record with a valid source passes and the table is neither
+ *   read nor written. n = 0 writes only the summary. WG_HS_RL_COMPACT in flags: the call first drops the stale
+ *   entries (wg_hs_rl_compact's launches) exactly when U + min(*n_records, n) > C / 2 and *now != 0. Without a
+ *   reserve or a config: WG_ENOKEY. records, out_records: 16-byte aligned; src, now, rl_summary: 8; the others: 4.
+ *   An output (rl_status, out_records, rl_summary) that overlaps another output or an input: WG_EINVAL. n above
+ *   2^30: WG_E2BIG. A capturing stream that would have to allocate: WG_EINVAL. 7 + burst launches (+ 3 with
+ *   WG_HS_RL_COMPACT), fixed by the call and the config and never by the data; no workgroup waits for another;
+ *   nothing about a call lives on the host, so a captured admit + ratelimit + dh replays with only *now refreshed.
+ *   Streams of one context are ordered by the library.
+ * wg_hs_rl_compact(ctx, now, summary_dev, stream): rebuilds the table from the entries with (*now >= last ? *now -
+ *   last : 0) < max into the second buffer and flips the header's pointer (as wg_rx_sessions_compact does).
+ *   summary_dev (8-byte aligned, may be NULL) = {kept, dropped, 0, 0}. Three launches; capturable.
+ * wg_hs_rl_dump(ctx, out_host, max_entries, &n_out): the table's entries in table order, 32 bytes each; *n_out is
+ *   the table's count, of which the first min(count, max_entries) are written. wg_hs_rl_load(ctx, entries_host, n)
+ *   REPLACES the table's content (save and restore; n above C / 2: WG_ERANGE; a repeated key, a family that is
+ *   neither 4 nor 6, a non-zero pad byte or IPv4 tail: WG_EINVAL, nothing changes). wg_hs_rl_count(ctx, &used,
+ *   &capacity). All three are synchronous and ordered after everything queued before them.
+ * wg_ctx_destroy frees the table. Source addresses, statuses and bucket contents are public: nothing here touches a
+ *   secret, and there is no constant-time claim to make. The probe's hash is not keyed: a sender that chooses its
+ *   addresses can lengthen the walks of a table (never past C / 2 + 1 steps), not change an answer. */
+#define WG_HS_RL_MAX_BURST 16u
+#define WG_HS_RL_OK 0u
+#define WG_HS_RL_LIMITED 1u /* the source's bucket holds less than cost */
+#define WG_HS_RL_FULL 2u    /* an unknown source, and the table cannot take the call's unknown records */
+#define WG_HS_RL_BADSRC 3u  /* index >= n_src, or src.family is neither 4 nor 6 */
+#define WG_HS_RL_COMPACT 1u /* flags: drop the stale entries first if the call's records might not fit */
+typedef struct wg_hs_rl_entry { /* 32 bytes */
+  uint8_t addr[8];              /* the key's bytes: addr[0..4) and zeros (family 4), addr[0..8) (family 6) */
+  uint8_t family;               /* 4 or 6 */
+  uint8_t _pad[7];
+  uint64_t tokens;
+  uint64_t last;
+} wg_hs_rl_entry;
+typedef struct wg_hs_rl_summary {
+  uint32_t n_passed, n_limited, n_full, n_badsrc;
+} wg_hs_rl_summary;
+typedef struct wg_hs_rl_compact_summary {
+  uint32_t kept, dropped, _zero[2];
+} wg_hs_rl_compact_summary;
+typedef struct wg_hs_rl_batch {
+  const wg_hs_record* records;  /* device, 16-byte aligned, n entries */
+  const uint32_t* n_records;    /* device (&wg_hs_summary.n_valid), or NULL: all n */
+  const wg_hs_src* src;         /* device, 8-byte aligned, n_src entries, by batch index */
+  const uint64_t* now;          /* device, 8-byte aligned: the tick count */
+  uint32_t* rl_status;          /* device, n entries, WG_HS_RL_*, by record position */
+  wg_hs_record* out_records;    /* device, 16-byte aligned, n entries */
+  wg_hs_rl_summary* rl_summary; /* device, 16 bytes, 8-byte aligned */
+  uint32_t n, n_src;
+  uint32_t flags;               /* WG_HS_RL_COMPACT */
+  uint32_t _reserved;
+} wg_hs_rl_batch;
+int wg_hs_rl_reserve(wg_ctx* ctx, uint32_t max_sources);
+int wg_hs_rl_config_set(wg_ctx* ctx, uint64_t cost, uint32_t burst);
+int wg_hs_ratelimit(wg_ctx* ctx, const wg_hs_rl_batch* batch, void* stream);
+int wg_hs_rl_compact(wg_ctx* ctx, const uint64_t* now_dev, wg_hs_rl_compact_summary* summary_dev, void* stream);
+int wg_hs_rl_dump(wg_ctx* ctx, wg_hs_rl_entry* out_host, uint32_t max_entries, uint32_t* n_out);
+int wg_hs_rl_load(wg_ctx* ctx, const wg_hs_rl_entry* entries_host, uint32_t n);
+int wg_hs_rl_count(wg_ctx* ctx, uint32_t* used, uint32_t* capacity);
 
 /* ---- handshake sessions installed on the device ----
  * What the reference does with a finished handshake (SessionManager.setSession: a new EstablishedSession around a

@@ -19,3 +19,4 @@ from .engine import WG_HS_PENDING_DTYPE, WG_HS_ESTABLISHED_DTYPE  # noqa: F401
 from .engine import TimersConfig, WG_TIMER_SLOT_DTYPE, WG_TIMER_PEER_STATE_DTYPE, WG_TIMER_EXPIRED_DTYPE  # noqa: F401
 from .engine import WG_HS_SRC_DTYPE, WG_HS_COOKIE_REPLY_DTYPE, WG_HS_LEARNED_DTYPE  # noqa: F401
 from .engine import WG_TX_ITEM_DTYPE  # noqa: F401
+from .engine import RateLimitConfig, WG_HS_RL_ENTRY_DTYPE  # noqa: F401

@@ -63,6 +63,12 @@ WG_HS_MAC2_OK = 0
 WG_HS_MAC2_NONE = 1
 WG_HS_MAC2_BADDESC = 2
 WG_HS_MAC2_BADPEER = 3
+WG_HS_RL_MAX_BURST = 16
+WG_HS_RL_OK = 0
+WG_HS_RL_LIMITED = 1
+WG_HS_RL_FULL = 2
+WG_HS_RL_BADSRC = 3
+WG_HS_RL_COMPACT = 1
 WG_HS_INIT_SIZE = 148
 WG_HS_RESP_SIZE = 92
 WG_X25519_OK = 0
@@ -382,6 +388,31 @@ class WgHsMac2Batch(ctypes.Structure):
                 ("summary", ctypes.c_void_p), ("n", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
 
 
+class WgHsRlEntry(ctypes.Structure):
+    """wg_hs_rl_entry: one source's bucket of the rate limiter (wg_hs_rl_dump / wg_hs_rl_load)."""
+    _fields_ = [("addr", ctypes.c_uint8 * 8), ("family", ctypes.c_uint8), ("_pad", ctypes.c_uint8 * 7),
+                ("tokens", ctypes.c_uint64), ("last", ctypes.c_uint64)]
+
+
+class WgHsRlSummary(ctypes.Structure):
+    """wg_hs_rl_summary: totals of one wg_hs_ratelimit call."""
+    _fields_ = [("n_passed", ctypes.c_uint32), ("n_limited", ctypes.c_uint32), ("n_full", ctypes.c_uint32),
+                ("n_badsrc", ctypes.c_uint32)]
+
+
+class WgHsRlCompactSummary(ctypes.Structure):
+    """wg_hs_rl_compact_summary: totals of one wg_hs_rl_compact call."""
+    _fields_ = [("kept", ctypes.c_uint32), ("dropped", ctypes.c_uint32), ("_zero", ctypes.c_uint32 * 2)]
+
+
+class WgHsRlBatch(ctypes.Structure):
+    """wg_hs_rl_batch: one wg_hs_ratelimit call (device pointers)."""
+    _fields_ = [("records", ctypes.c_void_p), ("n_records", ctypes.c_void_p), ("src", ctypes.c_void_p),
+                ("now", ctypes.c_void_p), ("rl_status", ctypes.c_void_p), ("out_records", ctypes.c_void_p),
+                ("rl_summary", ctypes.c_void_p), ("n", ctypes.c_uint32), ("n_src", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
+
+
 class WgHsInstallSummary(ctypes.Structure):
     """wg_hs_install_summary: totals of one wg_hs_install call."""
     _fields_ = [("n_ok", ctypes.c_uint32), ("n_badslot", ctypes.c_uint32), ("n_dup", ctypes.c_uint32),
@@ -608,6 +639,13 @@ SIGNATURES = [
     ("wg_hs_cookies_get", _I, [_VP, _U32, _U32, _VP, _VP]),
     ("wg_hs_cookies_set", _I, [_VP, _U32, _U32, _VP, _VP]),
     ("wg_hs_mac2", _I, [_VP, ctypes.POINTER(WgHsMac2Batch), _VP]),
+    ("wg_hs_rl_reserve", _I, [_VP, _U32]),
+    ("wg_hs_rl_config_set", _I, [_VP, _U64, _U32]),
+    ("wg_hs_ratelimit", _I, [_VP, ctypes.POINTER(WgHsRlBatch), _VP]),
+    ("wg_hs_rl_compact", _I, [_VP, _VP, _VP, _VP]),
+    ("wg_hs_rl_dump", _I, [_VP, _VP, _U32, ctypes.POINTER(_U32)]),
+    ("wg_hs_rl_load", _I, [_VP, _VP, _U32]),
+    ("wg_hs_rl_count", _I, [_VP, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
     ("wg_rx_sessions_reserve", _I, [_VP, _U32]),
     ("wg_rx_sessions_retire", _I, [_VP, _VP, _U32, _VP, _VP]),
     ("wg_rx_sessions_count", _I, [_VP, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),

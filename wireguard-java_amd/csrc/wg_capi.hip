@@ -827,6 +827,7 @@ int launch_after_seal(wg_ctx* c, const wg_batch* sb, const wg_batch* ob, hipStre
 #include "wg_hs_install.hip"
 #include "wg_hs_stamp.hip"
 #include "wg_hs_cookie.hip"
+#include "wg_hs_ratelimit.hip"
 #include "wg_timers.hip"
 #include "wg_endpoints.hip"
 

@@ -101,6 +101,12 @@ struct HsState {
   // wg_hs_cookie.hip: the cookie table's header (fixed address) and the table of wg_hs_peers_set's peers
   DevBuf d_chdr, d_cook;
   bool has_secret = false;
+  // wg_hs_ratelimit.hip, allocated by wg_hs_rl_reserve (rl_cap != 0): the limiter's header (fixed address), the
+  // table's two buffers (rl_cap + 1 entries each), per bucket the call's count and selection row; per record the
+  // call's {bucket, code, key} (16 B), per range its counts
+  DevBuf d_rlhdr, d_rlent[2], d_rlcnt, d_rlrows, d_rlrec, d_rlpart;
+  uint32_t rl_cap = 0;    // the table's capacity C (the compaction's grid)
+  uint32_t rl_burst = 0;  // wg_hs_rl_config_set's burst (0: no config yet): the selection launches of a call
   uint32_t reserved = 0;  // the greatest wg_hs_reserve so far: what the stamp's scratch starts with
   uint32_t n_peers = 0;
   bool has_key = false;
@@ -229,6 +235,18 @@ int hs_stamp_grow(HsState* t, uint32_t n) {
   int rc;
   if ((rc = t->d_spart.ensure((size_t)std::max(rank_blocks(n), 1u) * 16)) != WG_OK) return rc;
   return t->d_sres.ensure((size_t)std::max(n, 1u) * 16);
+}
+
+// the scratch of wg_hs_ratelimit for n records (16 B per record, per range its counts), and its growth; a context
+// without a limiter has none
+bool hs_rl_fits(const HsState* t, uint32_t n) {
+  return !t->rl_cap || ((size_t)std::max(rank_blocks(n), 1u) * 16 <= t->d_rlpart.cap && (size_t)std::max(n, 1u) * 16 <= t->d_rlrec.cap);
+}
+int hs_rl_grow(HsState* t, uint32_t n) {
+  if (!t->rl_cap) return WG_OK;
+  int rc;
+  if ((rc = t->d_rlpart.ensure((size_t)std::max(rank_blocks(n), 1u) * 16)) != WG_OK) return rc;
+  return t->d_rlrec.ensure((size_t)std::max(n, 1u) * 16);
 }
 
 int hs_begin(HsState* t, hipStream_t s, bool capturing, uint32_t n, bool open, const PlanWords& w) {
@@ -609,11 +627,12 @@ int wg_hs_reserve(wg_ctx* c, uint32_t max_messages) {
   const uint32_t pend = std::min(max_messages, 0x10000000u);  // (wg_hs_finish takes no more pending entries)
   t->reserved = std::max(t->reserved, max_messages);
   return plan_reserve(hs_scratch_fits(t, max_messages, true) && hs_resp_fits(t, max_messages) && hs_init_fits(t, max_messages, pend) &&
-                          hs_stamp_fits(t, max_messages),
+                          hs_stamp_fits(t, max_messages) && hs_rl_fits(t, max_messages),
                       [&] {
                         int grc = hs_scratch_grow(t, max_messages, true);
                         if (grc == WG_OK) grc = hs_resp_grow(t, max_messages);
                         if (grc == WG_OK) grc = hs_stamp_grow(t, max_messages);
+                        if (grc == WG_OK) grc = hs_rl_grow(t, max_messages);
                         return grc != WG_OK ? grc : hs_init_grow(t, max_messages, pend);
                       });
 }

@@ -53,6 +53,8 @@ WG_HS_ESTABLISHED_DTYPE = np.dtype([("index", "<u4"), ("record", "<u4"), ("pendi
 WG_HS_SRC_DTYPE = np.dtype([("addr", "u1", (16,)), ("port", "u1", (2,)), ("family", "u1"), ("_pad", "u1", (5,))])
 WG_HS_COOKIE_REPLY_DTYPE = np.dtype([("index", "<u4"), ("len", "<u4"), ("msg", "u1", (64,)), ("_pad", "<u4", (2,))])
 WG_HS_LEARNED_DTYPE = np.dtype([("index", "<u4"), ("pending", "<u4"), ("peer", "<u4"), ("_zero", "<u4")])
+WG_HS_RL_ENTRY_DTYPE = np.dtype([("addr", "u1", (8,)), ("family", "u1"), ("_pad", "u1", (7,)), ("tokens", "<u8"),
+                                 ("last", "<u8")])
 WG_TX_ITEM_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("key_slot", "<u4"), ("peer", "<u4"), ("index", "<u4"),
                              ("dst", WG_HS_SRC_DTYPE)])
 WG_TIMER_SLOT_DTYPE = np.dtype([("state", "<u4"), ("peer", "<u4"), ("local_index", "<u4"), ("partner", "<u4"),
@@ -93,6 +95,22 @@ class TimersConfig:
 
     def as_struct(self) -> "L.WgTimersConfig":
         return L.WgTimersConfig(*(getattr(self, f) for f in self.FIELDS))
+
+
+class RateLimitConfig:
+    """The handshake rate limiter's two numbers (wg_hs_rl_config_set): `cost` ticks per handshake, `burst` handshakes."""
+
+    def __init__(self, cost: int, burst: int):
+        self.cost, self.burst = int(cost), int(burst)
+
+    @classmethod
+    def wireguard(cls, ticks_per_second: int) -> "RateLimitConfig":
+        """WireGuard's constants: 20 handshakes per second and source, a burst of 5."""
+        return cls(ticks_per_second // 20, 5)
+
+    @property
+    def max(self) -> int:
+        return self.cost * self.burst
 
 
 def pack_b2s_desc(in_off, out_off, key_off, length, outlen, keylen) -> np.ndarray:
@@ -1079,6 +1097,60 @@ class Engine:
         b = L.WgHsMac2Batch(records.data_ptr(), peer.data_ptr(), mac2_status.data_ptr(), summary.data_ptr(),
                             records.shape[0], 0)
         L.check(self._lib.wg_hs_mac2(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    # ---- handshakes rate-limited per source (wg_hs_rl_* / wg_hs_ratelimit) ----
+    def hs_rl_reserve(self, max_sources: int) -> None:
+        """wg_hs_rl_reserve: the limiter's table, for up to max_sources sources at once (capacity: the smallest power
+        of two >= max(8, 2 max_sources)), with its spare and scratch. hs_reserve() sizes the per-record scratch."""
+        L.check(self._lib.wg_hs_rl_reserve(self.ctx, max_sources))
+
+    def hs_rl_config_set(self, config, burst: int | None = None) -> None:
+        """wg_hs_rl_config_set: a RateLimitConfig, or (cost, burst). A new cost needs no re-capture of a captured
+        hs_ratelimit(); a greater burst does."""
+        cost, burst = (config.cost, config.burst) if burst is None else (config, burst)
+        if cost < 0 or cost >= 1 << 64 or burst < 0 or burst >= 1 << 32:
+            raise L.WgError(L.WG_EINVAL, f"ratelimit cost {cost}, burst {burst}")
+        L.check(self._lib.wg_hs_rl_config_set(self.ctx, cost, burst))
+
+    def hs_ratelimit(self, records, hs_summary, src, now, rl_status, out_records, rl_summary, compact: bool = False,
+                     stream: int | None = None) -> None:
+        """wg_hs_ratelimit over torch tensors: records uint8 [n, 160] as hs_check() / hs_admit() wrote them, hs_summary
+        the int32 [4] tensor whose first word is their count (n_valid), or None for all n; src uint8 [n_src, 24]
+        (WG_HS_SRC_DTYPE, by batch index), now int64 [1] (ticks; 0: nothing is limited), rl_status int32 [n]
+        (WG_HS_RL_*, by record position), out_records uint8 [n, 160] (the OK records, in order), rl_summary int32 [4]
+        (n_passed, n_limited, n_full, n_badsrc): hs_dh() takes it as its hs_summary. compact: drop the stale entries
+        first if the call's records might not fit the table."""
+        b = L.WgHsRlBatch(records.data_ptr(), hs_summary.data_ptr() if hs_summary is not None else None,
+                          src.data_ptr() if src.shape[0] else None, now.data_ptr(), rl_status.data_ptr(),
+                          out_records.data_ptr(), rl_summary.data_ptr(), records.shape[0], src.shape[0],
+                          L.WG_HS_RL_COMPACT if compact else 0, 0)
+        L.check(self._lib.wg_hs_ratelimit(self.ctx, ctypes.byref(b), stream if stream is not None else _torch_stream()))
+
+    def hs_rl_compact(self, now, summary=None, stream: int | None = None) -> None:
+        """wg_hs_rl_compact: rebuild the limiter's table from the entries that are not stale at *now (int64 [1]);
+        summary int32 [4] (kept, dropped, 0, 0) or None."""
+        L.check(self._lib.wg_hs_rl_compact(self.ctx, now.data_ptr(), summary.data_ptr() if summary is not None else None,
+                                           stream if stream is not None else _torch_stream()))
+
+    def hs_rl_count(self) -> tuple[int, int]:
+        """wg_hs_rl_count: (entries, capacity) of the limiter's table."""
+        used, cap = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        L.check(self._lib.wg_hs_rl_count(self.ctx, ctypes.byref(used), ctypes.byref(cap)))
+        return used.value, cap.value
+
+    def hs_rl_dump(self) -> np.ndarray:
+        """wg_hs_rl_dump: the limiter's entries, in table order (WG_HS_RL_ENTRY_DTYPE)."""
+        used, _ = self.hs_rl_count()
+        out = np.zeros(used, WG_HS_RL_ENTRY_DTYPE)
+        n = ctypes.c_uint32(0)
+        L.check(self._lib.wg_hs_rl_dump(self.ctx, out.ctypes.data if used else None, used, ctypes.byref(n)))
+        return out[:min(used, n.value)]
+
+    def hs_rl_load(self, entries) -> None:
+        """wg_hs_rl_load: replace the limiter's entries with these (WG_HS_RL_ENTRY_DTYPE, as hs_rl_dump() returned
+        them): save and restore."""
+        ent = np.ascontiguousarray(entries, WG_HS_RL_ENTRY_DTYPE)
+        L.check(self._lib.wg_hs_rl_load(self.ctx, ent.ctypes.data if ent.size else None, ent.size))
 
     def hs_stamp_host(self, init_entry, record, shared):
         """One wg_hs_init entry (a WG_HS_INIT_DTYPE scalar, as hs_open_host() returned it) with the record it came

@@ -6,4 +6,5 @@ from .crypto import (AEADBadTagException, BadPaddingException, Blake2s, BLAKE2s2
                      ChaCha20Poly1305, Crypto, HChaCha20, IllegalStateException, Poly1305, XChaCha20Poly1305,
                      calculate_cookie, calculate_mac1, calculate_mac2)
 from .handshake import Handshakes, InitiatorStageOne, ResponderHandshake, SymmetricKeypair  # noqa: F401
+from .ratelimit import RateLimiter, ratelimit_key  # noqa: F401
 from .keys import NoisePresharedKey, NoisePrivateKey, NoisePublicKey, X25519  # noqa: F401
